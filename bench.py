@@ -11,6 +11,18 @@ random-init weights (no network access in this environment).
         --master-addr 127.0.0.1 bench.py --gpus 8 --steps 30 --warmup 10
 
 One rank per GPU over RCCL; rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps train steps and prints the
+result line. --full adds the measurements the headline figure does not
+need (the multi-GPU 64 MiB all-reduce bandwidth probe). --dump-outputs
+DIR writes what one step of the timed path returns, its loss dict, as
+DIR/<name>.npy; together with --full it adds a seeded sample of that
+step's gradients and updated parameters (not reproducible on the GPU, see
+step_outputs). Model init, disparity sampling and data are seeded. The
+timed loop is the same with and without the option; the dumped step is
+run once more after the clock has stopped, from the seeded weights and a
+fresh Adam state on the last timed step's batch, so two builds run with
+the same arguments see identical inputs.
 """
 from __future__ import annotations
 
@@ -21,6 +33,79 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+DUMP_BYTE_LIMIT = 64 << 20
+
+
+def snapshot_state(task):
+    """Copies of the seeded parameters and buffers, for restore_state()."""
+    live = [t for m in (task.backbone, task.decoder)
+            for t in list(m.parameters()) + list(m.buffers())]
+    return live, [t.detach().clone() for t in live]
+
+
+def restore_state(task, snap) -> None:
+    """Put the model back to its seeded weights and Adam back to step 0,
+    all in place (the tensors keep their addresses, so a captured graph
+    and the gradient buckets stay valid)."""
+    import torch
+
+    live, saved = snap
+    with torch.no_grad():
+        for t, s in zip(live, saved):
+            t.copy_(s)
+        for st in task.optimizer.state.values():
+            for v in st.values():
+                if torch.is_tensor(v):
+                    v.zero_()
+
+
+SAMPLE_ELEMS = 1 << 20
+
+
+def step_outputs(task, loss_dict: dict, with_state: bool) -> dict:
+    """What one train step produced: the loss dict it returned and, with
+    with_state, a fixed seeded sample (SAMPLE_ELEMS elements each, drawn
+    over all parameters in optimizer order) of the reduced gradients it
+    left in .grad and of the parameters after its Adam update.
+
+    The samples sit behind --full because on the GPU they are not
+    reproducible: BatchNorm statistics are summed with fp32 atomics, the
+    random-init bf16 network amplifies that to bf16-epsilon differences on
+    most output elements, and the gradients of two identical steps then
+    differ by about their own norm (docs/NEXT.md section 7). The loss
+    terms, being means, agree to 1e-4 or better."""
+    import torch
+
+    out = {k: v for k, v in loss_dict.items() if torch.is_tensor(v)}
+    if not with_state:
+        return out
+    params = [p for g in task.optimizer.param_groups for p in g["params"]
+              if p.grad is not None]
+    with torch.no_grad():
+        grads = torch.cat([p.grad.reshape(-1).float() for p in params])
+        after = torch.cat([p.reshape(-1).float() for p in params])
+        idx = torch.randint(grads.numel(), (SAMPLE_ELEMS,),
+                            generator=torch.Generator().manual_seed(0))
+        idx = idx.sort().values.to(grads.device)
+        out["grad_sample"] = grads[idx]
+        out["param_sample"] = after[idx]
+    return out
+
+
+def dump_outputs(out_dir: str, outputs: dict) -> None:
+    """Write each tensor as <out_dir>/<name>.npy, float32."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in outputs.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    assert total <= DUMP_BYTE_LIMIT, total
 
 
 def main() -> int:
@@ -42,7 +127,18 @@ def main() -> int:
     p.add_argument("--timers", action="store_true",
                    help="print a sync-bracketed per-phase breakdown (diagnostic "
                         "run only; the extra syncs perturb the headline number)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements the headline figure "
+                        "does not need (multi-GPU: 64 MiB all-reduce "
+                        "bus-bandwidth probe; with --dump-outputs: gradient "
+                        "and updated-parameter samples)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, run the timed path once "
+                        "more from the seeded weights and write its loss "
+                        "dict as DIR/<name>.npy (fp32)")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -62,15 +158,17 @@ def main() -> int:
 
     if world_size > 1:
         # RCCL self-check BEFORE any model work (VERDICT round-1 item 6):
-        # a known-value all-reduce proves the collective path, and a
-        # 64 MiB ring probe prints the achieved bus bandwidth so the
-        # first multi-GPU run yields a diagnosable number.
+        # a known-value all-reduce proves the collective path.
         comm_dev = device if dist.get_backend() == "nccl" else "cpu"
         probe = torch.full((1,), float(rank + 1), device=comm_dev)
         dist.all_reduce(probe)
         expect = world_size * (world_size + 1) / 2
         assert abs(float(probe.item()) - expect) < 1e-3, \
             f"all-reduce self-check failed: {probe.item()} != {expect}"
+
+    if world_size > 1 and args.full:
+        # --full: a 64 MiB ring probe prints the achieved bus bandwidth
+        # so a multi-GPU run yields a diagnosable number.
         big = torch.ones(16 << 20, device=comm_dev)  # 64 MiB fp32
         for _ in range(2):
             dist.all_reduce(big)
@@ -104,7 +202,14 @@ def main() -> int:
     })
     state = RuntimeState(global_rank=rank, local_rank=local_rank,
                          world_size=world_size)
+    # Fixed seed (host and device generators): the random-init weights and
+    # the per-step disparity samples are the same in every run, so
+    # --dump-outputs of two builds can be compared output for output.
+    torch.manual_seed(20210829)
     task = SynthesisTask(cfg, state=state)
+    seeded = snapshot_state(task) if args.dump_outputs else None
+    # identical weights on every rank, distinct disparity samples per rank
+    torch.manual_seed(20210829 + 1 + rank)
 
     # Pre-build a few host-side batches; the H2D staging stays inside the
     # timed region (it is part of a real training step). Each rank gets
@@ -143,6 +248,23 @@ def main() -> int:
         step_fn(batches[i % len(batches)])
     sync()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs:
+        # The kernels accumulate with fp32 atomics and Adam turns that
+        # rounding noise into full-size weight updates, so after a few
+        # steps two runs hold visibly different weights. The dump therefore
+        # comes from one more step of the timed path, run after the clock
+        # has stopped, from the seeded weights and a zeroed Adam state on
+        # the last timed step's batch: it depends on the arguments alone.
+        # Every rank takes part (the step all-reduces); rank 0 writes.
+        restore_state(task, seeded)
+        torch.manual_seed(20210829 + 1 + rank)
+        outputs = step_outputs(
+            task, step_fn(batches[(args.steps - 1) % len(batches)]),
+            with_state=args.full)
+        sync()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
 
     # MAX elapsed over ranks = whole-job wall time
     if world_size > 1:

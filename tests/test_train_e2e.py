@@ -7,6 +7,15 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _cpu_only(env):
+    """Hide any GPU from the child processes: these runs are about the
+    gloo/CPU path, and two ranks must not land on one device over RCCL
+    when the machine happens to have a single GPU."""
+    env["HIP_VISIBLE_DEVICES"] = ""
+    env["CUDA_VISIBLE_DEVICES"] = ""
+    return env
+
+
 def test_train_cli_one_epoch(tmp_path):
     extra = {
         "data.name": "synthetic", "data.img_h": 64, "data.img_w": 64,
@@ -54,7 +63,7 @@ def test_video_cli_writes_frames(tmp_path):
 def test_bench_distributed_torchrun_cpu():
     """The driver's exact bench invocation shape (torchrun, one rank per
     GPU) — exercised with gloo on CPU, world_size 2."""
-    env = dict(os.environ)
+    env = _cpu_only(dict(os.environ))
     env["MASTER_ADDR"] = "127.0.0.1"
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
@@ -62,7 +71,7 @@ def test_bench_distributed_torchrun_cpu():
          "--master-port", "29611", os.path.join(ROOT, "bench.py"),
          "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "1",
          "--height", "128", "--width", "192", "--planes", "4",
-         "--dtype", "fp32"],
+         "--dtype", "fp32", "--full"],
         cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -70,6 +79,51 @@ def test_bench_distributed_torchrun_cpu():
     assert out["n_gpus"] == 2
     assert out["config"]["parallelism"] == "dp2"
     assert out["value"] > 0
+    # --full: the 64 MiB all-reduce probe reports on stderr
+    probe = [json.loads(l) for l in r.stderr.splitlines()
+             if l.startswith("{") and "busbw_GBps" in l]
+    assert len(probe) == 1 and probe[0]["rccl_selfcheck"] == "ok"
+    assert probe[0]["busbw_GBps"] > 0
+
+
+def test_bench_dump_outputs_roundtrip_cpu(tmp_path):
+    """--dump-outputs writes the loss dict, and with --full also gradient
+    and updated-parameter samples, as finite float32 arrays identical from
+    run to run on CPU; --steps and the result line are left alone."""
+    import numpy as np
+
+    def run(out_dir, *extra):
+        r = subprocess.run(
+            [sys.executable, os.path.join(ROOT, "bench.py"),
+             "--gpus", "1", "--steps", "2", "--warmup", "0", "--batch", "2",
+             "--height", "128", "--width", "192", "--planes", "4",
+             "--dtype", "fp32", "--dump-outputs", str(out_dir), *extra],
+            cwd=ROOT, env=_cpu_only(dict(os.environ)),
+            capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        res = json.loads([l for l in r.stdout.splitlines()
+                          if l.startswith("{")][-1])
+        assert res["steps"] == 2 and res["ms_per_step"] > 0
+        return {p.stem: np.load(p) for p in sorted(out_dir.glob("*.npy"))}
+
+    a, b = run(tmp_path / "a", "--full"), run(tmp_path / "b", "--full")
+    plain = run(tmp_path / "c")
+    state = {"grad_sample", "param_sample"}
+    assert {"loss", "loss_rgb_tgt", "loss_ssim_tgt"} | state <= set(a)
+    assert set(a) == set(b) and set(plain) == set(a) - state
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for name, v in a.items():
+        assert v.dtype == np.float32, name
+        assert np.isfinite(v).all(), name
+        np.testing.assert_array_equal(v, b[name], err_msg=name)
+        if name in plain:
+            np.testing.assert_array_equal(v, plain[name], err_msg=name)
+    assert a["loss"].shape == () and a["loss"] > 0
+    assert a["grad_sample"].size == a["param_sample"].size > 1000
+    # backward really ran: a tenth of the sample is a loose floor (at this
+    # tiny shape the deepest layers normalise two values per channel and
+    # pass exactly zero gradient upstream, so many entries are 0.0)
+    assert np.count_nonzero(a["grad_sample"]) > a["grad_sample"].size // 10
 
 
 def test_train_cli_two_ranks_gloo(tmp_path):
@@ -83,7 +137,7 @@ def test_train_cli_two_ranks_gloo(tmp_path):
         "training.eval_interval": 1000000, "data.num_workers": 0,
         "training.checkpoint_interval": 2,
     }
-    env = dict(os.environ)
+    env = _cpu_only(dict(os.environ))
     env["MASTER_ADDR"] = "127.0.0.1"
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",

@@ -1,7 +1,10 @@
 """Compare MIOpen find modes at the bench config; capture the tuned DB.
 
-Writes per-mode steady step times; MIOPEN_USER_DB_PATH must point into
-gpurun_out so the tuned find-db merges back for committing in-tree.
+Writes per-mode steady step times. MIOpen appends what it finds to the
+per-user copy of the find-db that importing mine_amd seeds from
+mine_amd/miopen_db (the path is printed below; a pre-set
+MIOPEN_USER_DB_PATH wins). To ship a tuned db, copy that directory's
+*.udb.txt / *.ufdb.txt over the files in mine_amd/miopen_db and commit.
 """
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,6 +16,8 @@ import torch
 from mine_amd.config import default_config
 from mine_amd.data import SyntheticMPIDataset, collate_src_tgt
 from mine_amd.engine import SynthesisTask
+
+print("MIOpen user db:", os.environ.get("MIOPEN_USER_DB_PATH", "(MIOpen default)"), flush=True)
 
 cfg = default_config(**{
     "data.name": "realestate10k", "data.img_h": 256, "data.img_w": 384,
