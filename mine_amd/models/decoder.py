@@ -69,7 +69,18 @@ class SplitConvBlock(nn.Module):
     profile showed MIOpen collapsing on (profiles/r01_progress.md). The
     single `conv` keeps the reference's (C_out, C_dec+C_enc+E, 3, 3)
     weight shape, so checkpoint keys and shapes are unchanged.
+
+    With a dec part, bf16 channels_last training on the GPU joins the
+    three terms inside the BN statistics pass (mine_amd/ops/bn.py
+    `join_stats`): one kernel writes the sum and accumulates its
+    per-channel (sum, sumsq), instead of materializing base+bias at batch
+    B*S, adding y_dec eagerly and letting BN read the result again. The
+    output is bit-identical to the eager join; `fused_join = False`, the
+    side stream, eval mode and every other dtype/layout keep the eager
+    code below.
     """
+
+    fused_join = True
 
     def __init__(self, dec_ch: int, base_ch: int, pe_ch: int, out_ch: int):
         super().__init__()
@@ -98,12 +109,15 @@ class SplitConvBlock(nn.Module):
             from mine_amd.ops.conv_general import conv2d_mfma
             y_base = conv2d_mfma(base, w[:, d:d + b].contiguous(),
                                  self.conv.bias, reflect=True)
-            K = y_base.shape[1]
             # PE part: conv of a spatially-constant field == channel bias
             w_pe = w[:, d + b:].sum((2, 3))  # (K, E)
             bias_pe = torch.matmul(pe.to(w_pe.dtype), w_pe.t())  # (B*S, K)
+            return y_base, bias_pe
+
+        def expand(y_base, bias_pe):
             # broadcast-add in NHWC so the (B*S,K,H,W) result is
             # channels_last without a transpose
+            K = y_base.shape[1]
             yb = y_base.permute(0, 2, 3, 1).unsqueeze(1) \
                 + bias_pe.view(B, S, 1, 1, K).to(y_base.dtype)
             return yb.view(B * S, y_base.shape[2], y_base.shape[3], K)
@@ -111,9 +125,9 @@ class SplitConvBlock(nn.Module):
         if use_side:
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                yb = base_part()
+                yb = expand(*base_part())
         else:
-            yb = base_part()
+            y_base, bias_pe = base_part()
 
         if d:
             from mine_amd.ops.conv import conv3x3_reflect
@@ -121,10 +135,21 @@ class SplitConvBlock(nn.Module):
             if use_side:
                 main.wait_stream(side)
                 yb.record_stream(main)
+            else:
+                # the fused join consumes y_dec, so it does not combine
+                # with the side stream
+                from mine_amd.ops.bn import join_stats, join_stats_usable
+                if self.fused_join and self.bn.training \
+                        and join_stats_usable(y_dec, y_base):
+                    x, sums = join_stats(y_dec, y_base, bias_pe, B, S)
+                    return self.bn(x, sums=sums)
+                yb = expand(y_base, bias_pe)
             yb = yb + y_dec.permute(0, 2, 3, 1)
         elif use_side:
             main.wait_stream(side)
             yb.record_stream(main)
+        else:
+            yb = expand(y_base, bias_pe)
         return self.bn(yb.permute(0, 3, 1, 2))
 
 

@@ -48,15 +48,62 @@ class _BNActFn(torch.autograd.Function):
         # SyncBN backward: dx needs the GLOBAL (dbeta, dgamma) sums and the
         # global batch count; the returned parameter grads stay LOCAL (DDP
         # averages them afterwards, matching torch SyncBatchNorm + DDP).
-        dbeta, dgamma = red[:C].clone(), red[C:].clone()
+        # Only the in-place all-reduce below overwrites `red`, so the local
+        # grads need copies under sync alone; otherwise views do.
+        dbeta, dgamma = red[:C], red[C:]
         M_norm = M
         if sync:
+            dbeta, dgamma = dbeta.clone(), dgamma.clone()
             torch.distributed.all_reduce(red)
             M_norm = M * torch.distributed.get_world_size()
         dx, dres = ext.bn_act_bwd_dx(x_flat, res_flat, gy, mean, invstd,
                                      gamma, beta, red, M, C, act, M_norm)
         return (dx, dres if act == _ACT["add_relu"] else None, None, None,
                 dgamma, dbeta, None, None, None, None)
+
+
+class _JoinStatsFn(torch.autograd.Function):
+    """x = (y_base[b] + bias[b,s]) + y_dec[b,s] with the per-channel
+    (sum, sumsq) of x from the same pass (bn_join_stats_vec_kernel).
+
+    y_dec (B*S,K,H,W) and y_base (B,K,H,W) are bf16 channels_last, bias is
+    bf16 (B*S,K). x is bit-identical to the eager bf16 chain."""
+
+    @staticmethod
+    def forward(ctx, y_dec, y_base, bias, B, S):
+        ext = get_extension(required=True)
+        _, K, H, W = y_dec.shape
+        x_flat, sums = ext.bn_join_stats(
+            y_dec.permute(0, 2, 3, 1).reshape(-1),
+            y_base.permute(0, 2, 3, 1).reshape(-1),
+            bias.contiguous(), B, S, H * W, K)
+        ctx.geom = (B, S, H, W, K)
+        ctx.mark_non_differentiable(sums)
+        return x_flat.view(B * S, H, W, K).permute(0, 3, 1, 2), sums
+
+    @staticmethod
+    def backward(ctx, g, _gsums):
+        B, S, H, W, K = ctx.geom
+        g_nhwc = g.permute(0, 2, 3, 1)
+        g_base = g_nhwc.reshape(B, S, H, W, K).sum(1).permute(0, 3, 1, 2)
+        return g, g_base, g_nhwc.sum((1, 2)), None, None
+
+
+def join_stats_usable(y_dec: torch.Tensor, y_base: torch.Tensor) -> bool:
+    """True where the fused join kernel applies: bf16 channels_last on the
+    GPU with a 16-byte channel vector; everything else joins eagerly."""
+    return (y_dec.is_cuda and y_dec.dim() == 4
+            and y_dec.dtype == torch.bfloat16
+            and y_base.dtype == torch.bfloat16
+            and y_dec.shape[1] % 8 == 0
+            and y_dec.is_contiguous(memory_format=torch.channels_last)
+            and y_base.is_contiguous(memory_format=torch.channels_last))
+
+
+def join_stats(y_dec, y_base, bias, B: int, S: int):
+    """Fused SplitConvBlock join; returns (x, sums) with sums the (2C,)
+    fp32 buffer `FusedBNAct.forward(x, sums=sums)` consumes."""
+    return _JoinStatsFn.apply(y_dec, y_base, bias.to(torch.bfloat16), B, S)
 
 
 def _act_eager(act: str, z: torch.Tensor) -> torch.Tensor:
@@ -100,7 +147,11 @@ class FusedBNAct(nn.BatchNorm2d):
             z = _act_eager(self.act, z)
         return z.to(x.dtype)
 
-    def forward(self, x: torch.Tensor, res: torch.Tensor = None):
+    def forward(self, x: torch.Tensor, res: torch.Tensor = None,
+                sums: torch.Tensor = None):
+        """`sums`: optional precomputed fp32 (2C,) per-channel (sum, sumsq)
+        of `x` (from `join_stats`); the training path then skips its own
+        statistics launch. Ignored by the fallback and in eval mode."""
         assert (res is not None) == (self.act == "add_relu")
         use_kernel = (
             x.is_cuda and x.dim() == 4
@@ -130,7 +181,8 @@ class FusedBNAct(nn.BatchNorm2d):
             track = self.track_running_stats and self.running_mean is not None
             empty = torch.empty(0, device=x.device, dtype=torch.float32)
             if do_sync:
-                sums = ext.bn_sums(x_flat.detach(), M, C)
+                if sums is None:
+                    sums = ext.bn_sums(x_flat.detach(), M, C)
                 torch.distributed.all_reduce(sums)
                 Mg = M * torch.distributed.get_world_size()
                 mean = sums[:C] / Mg
@@ -143,9 +195,15 @@ class FusedBNAct(nn.BatchNorm2d):
                         self.running_var += mom * (unbiased - self.running_var)
                 mean = mean.contiguous()
                 invstd = invstd.contiguous()
-            else:
+            elif sums is None:
                 mean, invstd = ext.bn_stats(
                     x_flat.detach(), M, C,
+                    self.running_mean if track else empty,
+                    self.running_var if track else empty,
+                    self.eps, mom)
+            else:
+                mean, invstd = ext.bn_finalize(
+                    sums, M, C,
                     self.running_mean if track else empty,
                     self.running_var if track else empty,
                     self.eps, mom)

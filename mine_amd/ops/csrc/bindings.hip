@@ -62,32 +62,35 @@ void mine_mpi_head_bwd_f32(const void*, const float*, void*, int64_t, int,
                            hipStream_t);
 void mine_mpi_head_bwd_bf16(const void*, const float*, void*, int64_t, int,
                             hipStream_t);
-void mine_bn_stats_f32(const void*, float*, int64_t, int, hipStream_t);
-void mine_bn_stats_bf16(const void*, float*, int64_t, int, hipStream_t);
+void mine_bn_stats_f32(const void*, float*, int64_t, int, int, hipStream_t);
+void mine_bn_stats_bf16(const void*, float*, int64_t, int, int, hipStream_t);
+void mine_bn_join_stats_bf16(const void*, const void*, const void*, void*,
+                             float*, int64_t, int, int, int, int,
+                             hipStream_t);
 void mine_bn_finalize(const float*, float*, float*, float*, float*, int64_t,
                       int, float, float, hipStream_t);
 void mine_bn_act_fwd_f32(const void*, const void*, const float*, const float*,
                          const float*, const float*, void*, int64_t, int, int,
-                         hipStream_t);
+                         int, hipStream_t);
 void mine_bn_act_fwd_bf16(const void*, const void*, const float*, const float*,
                           const float*, const float*, void*, int64_t, int, int,
-                          hipStream_t);
+                          int, hipStream_t);
 void mine_bn_act_bwd_reduce_f32(const void*, const void*, const void*,
                                 const float*, const float*, const float*,
-                                const float*, float*, int64_t, int, int,
+                                const float*, float*, int64_t, int, int, int,
                                 hipStream_t);
 void mine_bn_act_bwd_reduce_bf16(const void*, const void*, const void*,
                                  const float*, const float*, const float*,
-                                 const float*, float*, int64_t, int, int,
+                                 const float*, float*, int64_t, int, int, int,
                                  hipStream_t);
 void mine_bn_act_bwd_dx_f32(const void*, const void*, const void*,
                             const float*, const float*, const float*,
                             const float*, const float*, void*, void*, int64_t,
-                            int, int, hipStream_t);
+                            int, int, int, hipStream_t);
 void mine_bn_act_bwd_dx_bf16(const void*, const void*, const void*,
                              const float*, const float*, const float*,
                              const float*, const float*, void*, void*, int64_t,
-                             int, int, hipStream_t);
+                             int, int, int, hipStream_t);
 void mine_ssim_set_window(const float*);
 void mine_ssim_fwd(const float*, const float*, float*, int, int, int,
                    hipStream_t);
@@ -437,25 +440,26 @@ at::Tensor mpi_head_bwd(at::Tensor z, at::Tensor gout, int64_t N, bool alpha) {
   return gz;
 }
 
-at::Tensor bn_sums(at::Tensor x, int64_t M, int64_t C) {
+// max_blocks (trailing, default 0 = automatic) caps grid.x of the BN
+// launches so a test can run the strided row loop and its tail at a
+// small shape.
+at::Tensor bn_sums(at::Tensor x, int64_t M, int64_t C, int64_t max_blocks) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.numel() == M * C);
   auto sums = at::zeros({2 * C}, x.options().dtype(at::kFloat));
   BN_DISPATCH(mine_bn_stats, x.scalar_type(), x.data_ptr(),
-              sums.data_ptr<float>(), M, (int)C, stream());
+              sums.data_ptr<float>(), M, (int)C, (int)max_blocks, stream());
   return sums;
 }
 
-std::vector<at::Tensor> bn_stats(at::Tensor x, int64_t M, int64_t C,
-                                 at::Tensor running_mean,
-                                 at::Tensor running_var, double eps,
-                                 double momentum) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.numel() == M * C);
-  auto f32 = x.options().dtype(at::kFloat);
-  auto sums = at::zeros({2 * C}, f32);
-  BN_DISPATCH(mine_bn_stats, x.scalar_type(), x.data_ptr(),
-              sums.data_ptr<float>(), M, (int)C, stream());
-  auto mean = at::empty({C}, f32);
-  auto invstd = at::empty({C}, f32);
+// (sum, sumsq) -> (mean, invstd) + running-stat update
+std::vector<at::Tensor> bn_finalize(at::Tensor sums, int64_t M, int64_t C,
+                                    at::Tensor running_mean,
+                                    at::Tensor running_var, double eps,
+                                    double momentum) {
+  TORCH_CHECK(sums.is_cuda() && sums.is_contiguous() &&
+              sums.scalar_type() == at::kFloat && sums.numel() == 2 * C);
+  auto mean = at::empty({C}, sums.options());
+  auto invstd = at::empty({C}, sums.options());
   const bool track = running_mean.numel() > 0;
   mine_bn_finalize(sums.data_ptr<float>(), mean.data_ptr<float>(),
                    invstd.data_ptr<float>(),
@@ -465,31 +469,69 @@ std::vector<at::Tensor> bn_stats(at::Tensor x, int64_t M, int64_t C,
   return {mean, invstd};
 }
 
+std::vector<at::Tensor> bn_stats(at::Tensor x, int64_t M, int64_t C,
+                                 at::Tensor running_mean,
+                                 at::Tensor running_var, double eps,
+                                 double momentum, int64_t max_blocks) {
+  return bn_finalize(bn_sums(x, M, C, max_blocks), M, C, running_mean,
+                     running_var, eps, momentum);
+}
+
+// SplitConvBlock join fused into the stats pass (see bn_kernels.hip):
+// y_dec (B*S,HW,C), y_base (B,HW,C), bias (B*S,C), all flat bf16 NHWC.
+// Returns x = bf16(bf16(y_base + bias) + y_dec) and its (sum, sumsq).
+std::vector<at::Tensor> bn_join_stats(at::Tensor y_dec, at::Tensor y_base,
+                                      at::Tensor bias, int64_t B, int64_t S,
+                                      int64_t HW, int64_t C,
+                                      int64_t max_blocks) {
+  TORCH_CHECK(y_dec.is_cuda() && y_dec.is_contiguous() &&
+              y_base.is_contiguous() && bias.is_contiguous());
+  TORCH_CHECK(y_dec.scalar_type() == at::kBFloat16 &&
+              y_base.scalar_type() == at::kBFloat16 &&
+              bias.scalar_type() == at::kBFloat16,
+              "bn_join_stats: bf16 only");
+  TORCH_CHECK(C % 8 == 0 && B > 0 && S > 0 && HW > 0 &&
+              HW < (int64_t(1) << 31));
+  TORCH_CHECK(y_dec.numel() == B * S * HW * C &&
+              y_base.numel() == B * HW * C && bias.numel() == B * S * C);
+  auto x = at::empty_like(y_dec);
+  auto sums = at::zeros({2 * C}, y_dec.options().dtype(at::kFloat));
+  mine_bn_join_stats_bf16(y_dec.data_ptr(), y_base.data_ptr(),
+                          bias.data_ptr(), x.data_ptr(),
+                          sums.data_ptr<float>(), B * S * HW, (int)HW, (int)S,
+                          (int)C, (int)max_blocks, stream());
+  return {x, sums};
+}
+
 at::Tensor bn_act_fwd(at::Tensor x, at::Tensor res, at::Tensor mean,
                       at::Tensor invstd, at::Tensor gamma, at::Tensor beta,
-                      int64_t M, int64_t C, int64_t act) {
+                      int64_t M, int64_t C, int64_t act, int64_t max_blocks) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.numel() == M * C);
+  TORCH_CHECK(act >= 0 && act <= 4, "bn: unknown activation");
+  TORCH_CHECK(act != 4 || res.numel() == x.numel());
   auto y = at::empty_like(x);
   BN_DISPATCH(mine_bn_act_fwd, x.scalar_type(), x.data_ptr(),
               res.numel() ? res.data_ptr() : nullptr,
               mean.data_ptr<float>(), invstd.data_ptr<float>(),
               gamma.data_ptr<float>(), beta.data_ptr<float>(), y.data_ptr(),
-              M, (int)C, (int)act, stream());
+              M, (int)C, (int)act, (int)max_blocks, stream());
   return y;
 }
 
 at::Tensor bn_act_bwd_reduce(at::Tensor x, at::Tensor res, at::Tensor gy,
                              at::Tensor mean, at::Tensor invstd,
                              at::Tensor gamma, at::Tensor beta, int64_t M,
-                             int64_t C, int64_t act) {
+                             int64_t C, int64_t act, int64_t max_blocks) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && gy.is_contiguous());
+  TORCH_CHECK(act >= 0 && act <= 4, "bn: unknown activation");
   auto red = at::zeros({2 * C}, x.options().dtype(at::kFloat));
   const bool add_relu = act == 4;
   BN_DISPATCH(mine_bn_act_bwd_reduce, x.scalar_type(), x.data_ptr(),
               add_relu ? res.data_ptr() : nullptr, gy.data_ptr(),
               mean.data_ptr<float>(), invstd.data_ptr<float>(),
               gamma.data_ptr<float>(), beta.data_ptr<float>(),
-              red.data_ptr<float>(), M, (int)C, (int)act, stream());
+              red.data_ptr<float>(), M, (int)C, (int)act, (int)max_blocks,
+              stream());
   return red;  // (dbeta, dgamma)
 }
 
@@ -501,7 +543,8 @@ std::vector<at::Tensor> bn_act_bwd_dx(at::Tensor x, at::Tensor res,
                                       at::Tensor invstd, at::Tensor gamma,
                                       at::Tensor beta, at::Tensor red,
                                       int64_t M, int64_t C, int64_t act,
-                                      int64_t M_norm) {
+                                      int64_t M_norm, int64_t max_blocks) {
+  TORCH_CHECK(act >= 0 && act <= 4, "bn: unknown activation");
   const bool add_relu = act == 4;
   auto scaled = red;
   if (M_norm != M) {
@@ -509,15 +552,16 @@ std::vector<at::Tensor> bn_act_bwd_dx(at::Tensor x, at::Tensor res,
     // adding a second kernel parameter
     scaled = red * ((double)M / (double)M_norm);
   }
+  scaled = scaled.contiguous();
   auto dx = at::empty_like(x);
   auto dres = add_relu ? at::empty_like(x) : at::empty({0}, x.options());
   BN_DISPATCH(mine_bn_act_bwd_dx, x.scalar_type(), x.data_ptr(),
               add_relu ? res.data_ptr() : nullptr, gy.data_ptr(),
               mean.data_ptr<float>(), invstd.data_ptr<float>(),
               gamma.data_ptr<float>(), beta.data_ptr<float>(),
-              scaled.contiguous().data_ptr<float>(), dx.data_ptr(),
+              scaled.data_ptr<float>(), dx.data_ptr(),
               add_relu ? dres.data_ptr() : nullptr, M, (int)C, (int)act,
-              stream());
+              (int)max_blocks, stream());
   return {dx, dres};
 }
 
@@ -527,12 +571,12 @@ std::vector<at::Tensor> bn_act_bwd(at::Tensor x, at::Tensor res,
                                    at::Tensor beta, int64_t M, int64_t C,
                                    int64_t act) {
   auto red = bn_act_bwd_reduce(x, res, gy, mean, invstd, gamma, beta,
-                               M, C, act);
+                               M, C, act, 0);
   auto dxr = bn_act_bwd_dx(x, res, gy, mean, invstd, gamma, beta, red,
-                           M, C, act, M);
-  // dbeta = red[:C], dgamma = red[C:]
-  return {dxr[0], dxr[1], red.narrow(0, C, C).clone(),
-          red.narrow(0, 0, C).clone()};
+                           M, C, act, M, 0);
+  // dgamma = red[C:], dbeta = red[:C]; nothing writes `red` after the
+  // dx launch, so views suffice
+  return {dxr[0], dxr[1], red.narrow(0, C, C), red.narrow(0, 0, C)};
 }
 
 // --------------------------------------------------------------------------
@@ -610,15 +654,37 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "gather reflection pad over logical (N,H,W,C)");
   mod.def("reflect_pad_bwd", &reflect_pad_bwd,
           "gather (atomic-free) reflection pad backward");
+  namespace py = pybind11;
   mod.def("bn_stats", &bn_stats,
-          "per-channel mean/invstd + running-stat update");
+          "per-channel mean/invstd + running-stat update", py::arg("x"),
+          py::arg("M"), py::arg("C"), py::arg("running_mean"),
+          py::arg("running_var"), py::arg("eps"), py::arg("momentum"),
+          py::arg("max_blocks") = 0);
   mod.def("bn_sums", &bn_sums,
-          "per-channel (sum, sumsq) only — for cross-rank SyncBN");
-  mod.def("bn_act_fwd", &bn_act_fwd, "fused normalize + activation");
+          "per-channel (sum, sumsq) only — for cross-rank SyncBN",
+          py::arg("x"), py::arg("M"), py::arg("C"),
+          py::arg("max_blocks") = 0);
+  mod.def("bn_finalize", &bn_finalize,
+          "(sum, sumsq) -> mean/invstd + running-stat update");
+  mod.def("bn_join_stats", &bn_join_stats,
+          "x = (y_base + bias) + y_dec with its per-channel (sum, sumsq)",
+          py::arg("y_dec"), py::arg("y_base"), py::arg("bias"), py::arg("B"),
+          py::arg("S"), py::arg("HW"), py::arg("C"),
+          py::arg("max_blocks") = 0);
+  mod.def("bn_act_fwd", &bn_act_fwd, "fused normalize + activation",
+          py::arg("x"), py::arg("res"), py::arg("mean"), py::arg("invstd"),
+          py::arg("gamma"), py::arg("beta"), py::arg("M"), py::arg("C"),
+          py::arg("act"), py::arg("max_blocks") = 0);
   mod.def("bn_act_bwd", &bn_act_bwd,
           "fused BN+act backward -> dx, dres, dgamma, dbeta");
-  mod.def("bn_act_bwd_reduce", &bn_act_bwd_reduce);
-  mod.def("bn_act_bwd_dx", &bn_act_bwd_dx);
+  mod.def("bn_act_bwd_reduce", &bn_act_bwd_reduce, py::arg("x"),
+          py::arg("res"), py::arg("gy"), py::arg("mean"), py::arg("invstd"),
+          py::arg("gamma"), py::arg("beta"), py::arg("M"), py::arg("C"),
+          py::arg("act"), py::arg("max_blocks") = 0);
+  mod.def("bn_act_bwd_dx", &bn_act_bwd_dx, py::arg("x"), py::arg("res"),
+          py::arg("gy"), py::arg("mean"), py::arg("invstd"), py::arg("gamma"),
+          py::arg("beta"), py::arg("red"), py::arg("M"), py::arg("C"),
+          py::arg("act"), py::arg("M_norm"), py::arg("max_blocks") = 0);
   mod.def("mpi_head_fwd", &mpi_head_fwd,
           "dispconv out -> packed fp32 MPI (sigmoid rgb, |x|+1e-4 sigma)");
   mod.def("mpi_head_bwd", &mpi_head_bwd);

@@ -1,6 +1,15 @@
-"""Standalone timing of the fused BN kernels at the flagship shapes."""
-import os, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+"""Standalone timing of the fused BN kernels at the flagship shapes.
+
+    python tools/bn_bench.py [--root OTHER_CHECKOUT]
+
+--root imports mine_amd from another built checkout, so two builds can be
+timed with the same shape list.
+"""
+import argparse, os, sys, time
+ap = argparse.ArgumentParser()
+ap.add_argument("--root", default=os.path.dirname(
+    os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ap.parse_args().root)
 import torch
 from mine_amd.ops.bn import FusedBNAct
 
@@ -9,6 +18,8 @@ SHAPES = [  # (N, C, H, W) decoder's big BN layers + one encoder-ish
     (256, 32, 128, 192),
     (256, 16, 128, 192),
     (256, 64, 64, 96),
+    (256, 128, 32, 48),
+    (256, 64, 32, 48),
     (256, 256, 16, 24),
     (4, 64, 128, 192),
     (4, 256, 64, 96),
