@@ -9,14 +9,18 @@ Forward runs the hand-written v_mfma_f32_16x16x32_bf16 kernel
 padded tensor is ever materialized. Backward is hand-written too:
 dW on the split-K MFMA wrw kernel (ops/csrc/wrw_kernels.hip, reflect
 staged in LDS, fp32 atomics into the K x 9C output) and dX by driving
-the SAME fwd kernel in zero-embed mode over transposed/flipped weights
-plus the atomic-free reflect fold (identity proven in
+the SAME fwd kernel in zero-embed mode, its weights read transposed and
+flipped through the pack LUT, plus the atomic-free reflect fold (identity proven in
 tests/test_properties.py). MINE_CONV_BWD=miopen restores the round-1
 library backward for A/B comparison.
 
-Weights are re-packed to the exact MFMA fragment order each call (a
-cached index gather over the ~KxCx9 elements — microseconds); the
-fragment maps were measured on gfx950 with tools/mfma_probe.hip.
+Weights are gathered into the exact MFMA fragment order each call by
+one small kernel (ext.conv3x3_pack) through a cached index LUT. The
+data gradient uses a LUT of its own over the ORIGINAL (K,C,3,3) weight
+that folds in the transpose, the 180-degree flip and the zero-pad of a
+4-channel gradient to 8 — no transposed or flipped copy of the weight
+is ever made. The fragment maps were measured on gfx950 with
+tools/mfma_probe.hip.
 """
 from __future__ import annotations
 
@@ -28,6 +32,7 @@ import torch.nn.functional as F
 from mine_amd.ops.backend import get_extension
 
 _LUT_CACHE: Dict[Tuple[int, int, int, torch.device], torch.Tensor] = {}
+_BWD_LUT_CACHE: Dict[Tuple[int, int, torch.device], torch.Tensor] = {}
 
 
 def _pack_lut(K: int, C: int, flip: bool, device) -> torch.Tensor:
@@ -63,12 +68,76 @@ def _pack_lut(K: int, C: int, flip: bool, device) -> torch.Tensor:
     return lut
 
 
-def pack_weights(w: torch.Tensor, flip: bool = False) -> torch.Tensor:
-    """(K, C, 3, 3) -> fragment-ordered bf16 buffer."""
-    K, C = w.shape[0], w.shape[1]
-    lut = _pack_lut(K, C, flip, w.device)
+def _pack_lut_bwd(K: int, C: int, device) -> torch.Tensor:
+    """Index LUT of the data gradient's weights over the flattened
+    ORIGINAL (K,C,3,3) weight: the fragment order of
+    w.permute(1,0,2,3).flip(2,3) with its input channels (= K) zero-padded
+    to a multiple of 8. Pad entries hold the one-past-the-end index."""
+    key = (K, C, device)
+    lut = _BWD_LUT_CACHE.get(key)
+    if lut is not None:
+        return lut
+    Kp = (K + 7) & ~7
+    # fragment order of a (C, Kp, 3, 3) weight ...
+    fwd = _pack_lut(C, Kp, False, torch.device("cpu"))
+    zero_slot = K * C * 9
+    valid = fwd < C * Kp * 9
+    f = fwd.clamp(max=C * Kp * 9 - 1)
+    dx = f % 3
+    dy = (f // 3) % 3
+    k = (f // 9) % Kp          # its input channel  = w's output channel
+    c = f // (9 * Kp)          # its output channel = w's input channel
+    # ... read from w[k, c, 2-dy, 2-dx]
+    src = ((k * C + c) * 3 + (2 - dy)) * 3 + (2 - dx)
+    lut = torch.where(valid & (k < K), src,
+                      torch.full_like(src, zero_slot)).to(device)
+    _BWD_LUT_CACHE[key] = lut
+    return lut
+
+
+def _gather(w: torch.Tensor, lut: torch.Tensor) -> torch.Tensor:
+    if w.is_cuda and w.dtype in (torch.float32, torch.bfloat16):
+        ext = get_extension(required=True)
+        return ext.conv3x3_pack(w.detach().contiguous().reshape(-1), lut)
     flat = torch.cat((w.reshape(-1), w.new_zeros(1))).to(torch.bfloat16)
     return flat[lut].contiguous()
+
+
+def pack_weights(w: torch.Tensor, flip: bool = False) -> torch.Tensor:
+    """(K, C, 3, 3) -> fragment-ordered bf16 buffer (one gather kernel on
+    the GPU; index arithmetic on the CPU)."""
+    K, C = w.shape[0], w.shape[1]
+    return _gather(w, _pack_lut(K, C, flip, w.device))
+
+
+def pack_weights_bwd(w: torch.Tensor) -> torch.Tensor:
+    """(K, C, 3, 3) -> fragment-ordered bf16 buffer of the data
+    gradient's (C, ceil8(K), 3, 3) transposed, flipped weight."""
+    K, C = w.shape[0], w.shape[1]
+    return _gather(w, _pack_lut_bwd(K, C, w.device))
+
+
+def bias_grad(gy: torch.Tensor) -> torch.Tensor:
+    """Per-channel sum of a (B,K,H,W) channels_last gradient, fp32.
+
+    On the GPU in bf16 this is the BN statistics kernel's sum half: it
+    reads the bf16 gradient once at stream rate and makes no fp32 copy.
+    Like every BN statistic it combines per-block partials with fp32
+    atomics, so the last bits depend on the order the blocks finish in.
+    A 4-channel gradient is summed as (M/2, 8) and its halves added.
+    """
+    B, K, H, W = gy.shape
+    M = B * H * W
+    if (gy.is_cuda and gy.dtype == torch.bfloat16
+            and gy.is_contiguous(memory_format=torch.channels_last)):
+        ext = get_extension(required=True)
+        flat = gy.permute(0, 2, 3, 1).reshape(-1)
+        if K % 8 == 0:
+            return ext.bn_sums(flat, M, K, 0)[:K]
+        if K == 4 and M % 2 == 0:
+            s = ext.bn_sums(flat, M // 2, 8, 0)
+            return s[:4] + s[4:8]
+    return gy.float().sum((0, 2, 3))
 
 
 _BWD_MODE = None  # lazy: "hip" (hand-written MFMA) or "miopen" (round-1 path)
@@ -97,8 +166,7 @@ class _Conv3x3ReflFn(torch.autograd.Function):
         ext = get_extension(required=True)
         B, C, H, W = x.shape
         K = w.shape[0]
-        wb = w.to(torch.bfloat16)
-        wp = pack_weights(wb)
+        wp = pack_weights(w)
         x_flat = x.permute(0, 2, 3, 1).reshape(-1)  # NHWC view
         out = torch.empty(B * H * W * K, device=x.device, dtype=x.dtype)
         ext.conv3x3_fwd(x_flat, wp,
@@ -133,9 +201,9 @@ class _Conv3x3ReflFn(torch.autograd.Function):
                 xs.permute(0, 2, 3, 1).reshape(-1),
                 gy.permute(0, 2, 3, 1).reshape(-1),
                 B, H, W, C, K).view(K, C, 3, 3)
-            gb = gy.float().sum((0, 2, 3)) if ctx.has_bias else None
-            # dX: the SAME MFMA fwd kernel in zero-embed mode (transposed
-            # flipped weights) + the atomic-free reflect fold
+            gb = bias_grad(gy) if ctx.has_bias else None
+            # dX: the SAME MFMA fwd kernel in zero-embed mode (weights
+            # gathered transposed + flipped) + the atomic-free reflect fold
             gx = conv3x3_bwd_data(gy, w)
             return (gx, gw.to(w.dtype),
                     gb.to(w.dtype) if gb is not None else None)
@@ -192,7 +260,8 @@ def conv3x3_bwd_data(gy: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     kernel in zero-embed mode —
     gx = reflect_fold( conv_zero_pad2(gy, rot180(W).swap(0,1)) ), the
     identity verified on CPU in tests/test_properties.py and on GPU in
-    tests/test_gpu_ops.py.
+    tests/test_gpu_ops.py. rot180 and the swap live in the pack LUT
+    (_pack_lut_bwd), not in a copy of the weight.
 
     gy: (B, K, H, W) bf16 channels_last; w: (K, C, 3, 3). Returns
     gx (B, C, H, W) bf16 channels_last.
@@ -200,24 +269,24 @@ def conv3x3_bwd_data(gy: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     ext = get_extension(required=True)
     B, K, H, W = gy.shape
     C = w.shape[1]
-    if K % 8:
-        # the MFMA A-fragment loads 8 consecutive input channels (= K
-        # here): zero-pad the 4-channel dispconv gradient to 8
-        Kp = (K + 7) & ~7
+    # the MFMA B-fragment holds 8 consecutive input channels (= K here).
+    # The 4-channel dispconv gradient is staged by the kernel itself into
+    # the lower half of an 8-channel vector (c_mem = 4); the weight LUT
+    # zero-pads K to 8 — nothing is concatenated.
+    Kp = (K + 7) & ~7
+    if Kp != K and K != 4:
         gy = torch.cat(
             (gy, gy.new_zeros(B, Kp - K, H, W)), dim=1
         ).contiguous(memory_format=torch.channels_last)
-        w = torch.cat((w, w.new_zeros(Kp - K, C, 3, 3)), dim=0)
-        K = Kp
-    w_t = w.permute(1, 0, 2, 3).flip(2, 3).contiguous()  # (C, K, 3, 3)
-    wp = pack_weights(w_t.to(torch.bfloat16))
+    c_mem = 4 if K == 4 else Kp
+    wp = pack_weights_bwd(w)
     gy_flat = gy.permute(0, 2, 3, 1).reshape(-1)
     # logical image = gy zero-embedded by 1 ring -> output (H+2, W+2, C)
     gxp = torch.empty(B * (H + 2) * (W + 2) * C, device=gy.device,
                       dtype=torch.bfloat16)
     ext.conv3x3_fwd(gy_flat, wp,
                     torch.empty(0, device=gy.device, dtype=torch.float32),
-                    gxp, B, H + 2, W + 2, K, C, 1, H, W, 1)
+                    gxp, B, H + 2, W + 2, Kp, C, 1, H, W, 1, c_mem)
     gx = ext.reflect_pad_bwd(gxp, B, H, W, C, 1)
     return gx.view(B, H, W, C).permute(0, 3, 1, 2)
 

@@ -52,8 +52,10 @@ void mine_reflect_pad_bwd_f32(const float*, float*, int, int, int, int, int,
                               hipStream_t);
 void mine_reflect_pad_bwd_bf16(const void*, void*, int, int, int, int, int,
                                hipStream_t);
-void mine_conv3x3_fwd(const void*, const void*, const float*, void*, int,
-                      int, int, int, int, int, int, int, int, hipStream_t);
+int mine_conv3x3_fwd(const void*, const void*, const float*, void*, int, int,
+                     int, int, int, int, int, int, int, int, hipStream_t);
+void mine_conv3x3_pack(const void*, int, const int64_t*, void*, int64_t,
+                       int64_t, hipStream_t);
 void mine_conv3x3_wrw(const void*, const void*, float*, int, int, int, int,
                       int, hipStream_t);
 void mine_mpi_head_fwd_f32(const void*, float*, int64_t, int, hipStream_t);
@@ -380,21 +382,54 @@ at::Tensor reflect_pad_bwd(at::Tensor gout, int64_t N, int64_t H, int64_t W,
 // (src_h, src_w, off) back a zero-embedded logical image for the
 // transposed/data-grad use (pad_mode 1, off 1, logical = src + 2);
 // plain forward: src == logical, off == 0.
+// c_mem = channels per pixel of x in memory: 0 (= C), or 4 with C == 8
+// in zero-embed mode (the 4-channel dispconv gradient, staged into the
+// lower half of an 8-channel vector).
 void conv3x3_fwd(at::Tensor x_flat, at::Tensor wp, at::Tensor bias,
                  at::Tensor out, int64_t N, int64_t H, int64_t W, int64_t C,
                  int64_t K, int64_t pad_mode, int64_t src_h, int64_t src_w,
-                 int64_t off) {
-  TORCH_CHECK(x_flat.is_cuda() && x_flat.is_contiguous());
+                 int64_t off, int64_t c_mem) {
+  if (c_mem == 0) c_mem = C;
+  TORCH_CHECK(x_flat.is_cuda() && x_flat.is_contiguous() &&
+              wp.is_contiguous() && out.is_contiguous());
   TORCH_CHECK(x_flat.scalar_type() == at::kBFloat16 &&
               wp.scalar_type() == at::kBFloat16 &&
               out.scalar_type() == at::kBFloat16);
-  TORCH_CHECK(C % 8 == 0 && x_flat.numel() == N * src_h * src_w * C);
+  TORCH_CHECK(C % 8 == 0 && x_flat.numel() == N * src_h * src_w * c_mem);
   TORCH_CHECK(out.numel() == N * H * W * K);
-  mine_conv3x3_fwd(x_flat.data_ptr(), wp.data_ptr(),
-                   bias.numel() ? bias.data_ptr<float>() : nullptr,
-                   out.data_ptr(), (int)N, (int)H, (int)W, (int)C, (int)K,
-                   (int)pad_mode, (int)src_h, (int)src_w, (int)off,
-                   stream());
+  TORCH_CHECK(N > 0 && N <= 65535 && H > 0 && W > 0 && (H + 3) / 4 <= 65535);
+  TORCH_CHECK(wp.numel() ==
+              ((K + 15) / 16) * ((9 * (C / 8) + 3) / 4) * 64 * 8,
+              "conv3x3_fwd: packed weight size does not match (K, C)");
+  TORCH_CHECK(bias.numel() == 0 ||
+              (bias.numel() == K && bias.scalar_type() == at::kFloat &&
+               bias.is_contiguous()));
+  if (pad_mode == 0)
+    TORCH_CHECK(src_h == H && src_w == W && off == 0 && H >= 2 && W >= 2);
+  const int rc = mine_conv3x3_fwd(
+      x_flat.data_ptr(), wp.data_ptr(),
+      bias.numel() ? bias.data_ptr<float>() : nullptr, out.data_ptr(), (int)N,
+      (int)H, (int)W, (int)C, (int)c_mem, (int)K, (int)pad_mode, (int)src_h,
+      (int)src_w, (int)off, stream());
+  TORCH_CHECK(rc == 0, "conv3x3_fwd: no kernel for C=", C, " c_mem=", c_mem,
+              " pad_mode=", pad_mode);
+}
+
+// (K,C,3,3) weight (fp32 or bf16, flat) -> fragment-ordered bf16 buffer
+// through an int64 gather LUT; LUT entries == w.numel() read as zero.
+at::Tensor conv3x3_pack(at::Tensor w_flat, at::Tensor lut) {
+  TORCH_CHECK(w_flat.is_cuda() && w_flat.is_contiguous() && lut.is_cuda() &&
+              lut.is_contiguous() && lut.scalar_type() == at::kLong);
+  TORCH_CHECK(w_flat.scalar_type() == at::kFloat ||
+              w_flat.scalar_type() == at::kBFloat16,
+              "conv3x3_pack: weight must be f32 or bf16");
+  auto out = at::empty({lut.numel()}, w_flat.options().dtype(at::kBFloat16));
+  if (lut.numel())
+    mine_conv3x3_pack(w_flat.data_ptr(),
+                      w_flat.scalar_type() == at::kBFloat16 ? 1 : 0,
+                      lut.data_ptr<int64_t>(), out.data_ptr(), lut.numel(),
+                      w_flat.numel(), stream());
+  return out;
 }
 
 // Split-K MFMA weight gradient (see wrw_kernels.hip);
@@ -689,7 +724,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "dispconv out -> packed fp32 MPI (sigmoid rgb, |x|+1e-4 sigma)");
   mod.def("mpi_head_bwd", &mpi_head_bwd);
   mod.def("conv3x3_fwd", &conv3x3_fwd,
-          "fused reflect/zero-pad + 3x3 conv on MFMA 16x16x32 tiles");
+          "fused reflect/zero-pad + 3x3 conv on MFMA 16x16x32 tiles",
+          py::arg("x_flat"), py::arg("wp"), py::arg("bias"), py::arg("out"),
+          py::arg("N"), py::arg("H"), py::arg("W"), py::arg("C"), py::arg("K"),
+          py::arg("pad_mode"), py::arg("src_h"), py::arg("src_w"),
+          py::arg("off"), py::arg("c_mem") = 0);
+  mod.def("conv3x3_pack", &conv3x3_pack,
+          "gather a conv weight into MFMA fragment order (bf16)");
   mod.def("conv3x3_wrw", &conv3x3_wrw,
           "EXPERIMENTAL split-K MFMA weight gradient (unwired)");
 }

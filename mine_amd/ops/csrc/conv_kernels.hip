@@ -2,27 +2,52 @@
 // (the reference's ConvBlock conv, ref network/monodepth2/layers.py:106-138)
 //
 // The decoder's hot remaining convs are small-channel 3x3 blocks at
-// full resolution (16->16, 16->4, 32->16... at (B*S)=256 batch); MIOpen
-// reaches ~86 TF/s on them and needs the pad materialized. This kernel
-// folds the reflection pad into the LDS stage (no padded tensor ever
-// exists) and runs the GEMM on v_mfma_f32_16x16x32_bf16 tiles.
+// full resolution (16->16, 16->4, 32->16... at (B*S)=256 batch). They
+// are memory-bound: ~0.5 TFLOP against ~5 GB per direction per step.
+// This kernel folds the pad into the LDS stage (no padded tensor ever
+// exists) and is built so that instruction issue stays out of the way
+// of the stream: C and K are template parameters, every tap / segment /
+// LDS offset is a constant, and each lane stores whole 8-byte groups.
 //
 // Fragment layout (measured on gfx950 with tools/mfma_probe.hip):
 //   A:   row = lane & 15,  k = (lane>>4)*8 + e   (8 CONSECUTIVE k)
 //   B:   col = lane & 15,  k = (lane>>4)*8 + e
 //   C/D: col = lane & 15,  row = (lane>>4)*4 + r
 //
-// GEMM view: M = output pixels, N = K_out, K-dim = 9*C zero-padded to a
-// multiple of 32 in the order k = (seg)*8 + ci with seg = cb*9 + tap,
-// tap = dy*3 + dx, c = cb*8 + ci. A lane's 8 A-elements are then 8
-// consecutive input channels at ONE (dy, dx) tap: a single ds_read_b128
-// from the staged row. Weights arrive PRE-PACKED in exact fragment
-// order (mine_amd/ops/conv.py): one 16-byte global load per fragment.
+// GEMM view: A = WEIGHTS (row = output channel), B = PIXELS (col =
+// pixel). The A and B lane maps are identical, so the packed weight
+// fragments of mine_amd/ops/conv.py serve as A unchanged, and D comes
+// out with col = pixel, row = output channel: a lane holds channels
+// (lane>>4)*4 .. +3 of pixel lane&15 — one 8-byte store, 16 pixels x
+// 2K bytes contiguous per wave.
 //
-// Workgroup: 4 waves; output tile = one row y x 64 pixels x K_out.
-// LDS: 3 input rows x 66 pixels x C bf16, border handling (reflect for
-// the forward, zero for the transposed/data-gradient use) applied while
-// staging.
+// K-dim = 9*C zero-padded to a multiple of 32 in the order
+// k = seg*8 + ci, seg = cb*9 + tap, tap = dy*3 + dx, c = cb*8 + ci;
+// lane group g = lane>>4 of chunk kc carries seg = 4*kc + g. A lane's 8
+// B-elements are 8 consecutive input channels at ONE tap: a single
+// ds_read_b128. Each output element is the same sequence of fp32
+// products as in the first version of this kernel.
+//
+// Workgroup: 4 waves; output tile = TILE_H rows x 64 pixels x <=64
+// output channels; wave w owns pixels 16w..16w+15 of every row. The K
+// chunks are the OUTER (fully unrolled) loop: a chunk's weight
+// fragments are fetched once per tile and the TILE_H rows run under
+// them, accumulators TILE_H x NK x 4 VGPRs.
+//
+// LDS image, in 16-byte vectors (8 channels of one pixel):
+//   vec(cb, row, x) = cb*CB_PITCH + row*ROW_PITCH + x
+// with x the staged pixel 0..65 (input x0-1 .. x0+64), row 0..5.
+// ds_read_b128 is served in four groups of 16 lanes, each made of 8
+// lanes of an even g with pixels S and 8 lanes of the next g with the
+// complementary pixels S' (S = {0-3,12-15} or {4-11}); the group is
+// conflict-free iff the 16 vector indices are distinct mod 16 (or the
+// same address). The two g's hold consecutive segments:
+//   same (cb,dy), dx -> dx+1 : indices p+dx (p in S), p+dx+1 (p in S')
+//                              -> a window of 16, one shared address
+//   dx 2 -> 0, dy -> dy+1    : needs ROW_PITCH     == 2 (mod 16)
+//   tap 8 -> tap 0, cb -> +1 : needs CB_PITCH - 2*ROW_PITCH == 2
+// so ROW_PITCH = 66 (exactly the staged width) and CB_PITCH = 406
+// (6*66 + 10 pad vectors). tests/test_conv_lds_sim.py replays this map.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -38,6 +63,11 @@ constexpr int TILE_W = 64;          // output pixels per row tile
 constexpr int TILE_H = 4;           // output rows per workgroup
 constexpr int STAGE_W = TILE_W + 2; // 66
 constexpr int STAGE_H = TILE_H + 2; // 6 staged input rows (halo shared)
+constexpr int STAGE_BATCH = 7;      // 16-byte loads in flight per thread
+constexpr int ROW_PITCH = STAGE_W;                 // 66  == 2 (mod 16)
+constexpr int CB_PITCH = STAGE_H * ROW_PITCH + 10; // 406 == 6 (mod 16)
+static_assert(ROW_PITCH % 16 == 2 && (CB_PITCH - 2 * ROW_PITCH) % 16 == 2,
+              "LDS pitches must keep the B-fragment reads conflict-free");
 
 enum PadMode { PAD_REFLECT = 0, PAD_ZERO = 1 };
 
@@ -50,46 +80,122 @@ __device__ __forceinline__ int map_coord(int v, int n, int src_n, int off) {
   if (PAD == PAD_REFLECT) {
     if (v < 0) v = -v;
     if (v >= n) v = 2 * (n - 1) - v;
-    return v;
+    // rows/columns past the image (partial tiles) are staged but never
+    // stored; keep their source address inside the tensor
+    return min(max(v, 0), n - 1);
   }
   v -= off;
   return (v < 0 || v >= src_n) ? -1 : v;
 }
 
-template <int PAD>
-__global__ void __launch_bounds__(kBlock)
+// LDS vector offset of segment `seg` relative to (row 0, pixel 0). The
+// zero-padded segments past nseg re-read the last real one (their
+// fragment is zeroed after the read), which keeps their lane group on
+// the same conflict-free pattern.
+__host__ __device__ constexpr int seg_vec_off(int seg, int nseg) {
+  const int s = seg < nseg ? seg : nseg - 1;
+  const int cb = s / 9, tap = s % 9;
+  return cb * CB_PITCH + (tap / 3) * ROW_PITCH + (tap % 3);
+}
+
+// One staged vector per call: which (cb, row, x) thread `tid` handles in
+// pass `it`, kept as running counters so the loop has no division.
+template <int CV>
+struct StageIdx {
+  static constexpr int PX_STEP = kBlock / CV;       // pixels per pass
+  static constexpr int CV_STEP = kBlock % CV;
+  static constexpr int ROW_STEP = PX_STEP / STAGE_W;
+  static constexpr int X_STEP = PX_STEP % STAGE_W;
+  int cv, x, row;
+  __device__ __forceinline__ explicit StageIdx(int tid) {
+    cv = tid % CV;  // CV is a constant: mask or multiply
+    x = tid / CV;   // < 256
+    row = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      if (x >= STAGE_W) { x -= STAGE_W; ++row; }
+  }
+  __device__ __forceinline__ void next() {
+    x += X_STEP;
+    row += ROW_STEP;
+    if (CV_STEP) {
+      cv += CV_STEP;
+      if (cv >= CV) { cv -= CV; ++x; }
+    }
+    if (x >= STAGE_W) { x -= STAGE_W; ++row; }
+  }
+};
+
+// CV = input channels / 8, NK = 16-wide output-channel tiles of this
+// launch, CIN4 = the input tensor has 4 channels per pixel (the
+// dispconv gradient), staged with 8-byte loads into the lower half of
+// an 8-channel vector.
+//
+// Register budget: the second launch bound asks for 6 workgroups per CU
+// (6 waves/SIMD, what the first version of this kernel ran at) up to
+// K = 32; with the 48 / 64 accumulators of NK = 3 / 4 the compiler
+// needs 4 / 3 to stay out of scratch (C = 64 is at 3 by its LDS anyway).
+// KVEC: K % 4 == 0, so a lane's 4 channels go out as one 8-byte store.
+template <int PAD, int CV, int NK, bool CIN4, bool KVEC>
+__global__ void __launch_bounds__(kBlock, (NK <= 2 ? 6 : NK == 3 ? 4 : 3))
 conv3x3_fwd_kernel(const __hip_bfloat16* __restrict__ x,  // (N,sH,sW,C)
-                   const __hip_bfloat16* __restrict__ wp, // packed frags
+                   const bf16x8* __restrict__ wp,         // packed frags
                    const float* __restrict__ bias,        // (K) or null
                    __hip_bfloat16* __restrict__ out,      // (N,H,W,K)
-                   int H, int W, int C, int K,
+                   int H, int W, int K, int k0,
                    int sH, int sW, int off) {
-  extern __shared__ __hip_bfloat16 s_in[];  // [STAGE_H][STAGE_W][C]
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+  bf16x8* s_in = reinterpret_cast<bf16x8*>(s_raw);
+  constexpr int CPIX = CIN4 ? 4 : CV * 8;    // channels per pixel in memory
+  constexpr int NSEG = 9 * CV;               // segments of 8 k
+  constexpr int NCH = (NSEG + 3) / 4;        // 32-wide K chunks
+  constexpr int NIT = (STAGE_H * STAGE_W * CV + kBlock - 1) / kBlock;
+
   const int x0 = blockIdx.x * TILE_W;
   const int y0 = blockIdx.y * TILE_H;
   const int n = blockIdx.z;
   const int tid = threadIdx.x;
 
-  // ---- stage 6 reflected rows x 66 pixels x C (8-channel vectors) ----
-  const int Cv = C / 8;
-  const int total_v = STAGE_H * STAGE_W * Cv;
-  const int64_t x_n = (int64_t)n * sH * sW * C;
-  for (int i = tid; i < total_v; i += kBlock) {
-    const int cv = i % Cv;
-    const int rem = i / Cv;
-    const int sx = rem % STAGE_W;      // 0..65 -> input x = x0 + sx - 1
-    const int row = rem / STAGE_W;     // 0..5  -> input y = y0 + row - 1
-    const int yy = map_coord<PAD>(y0 + row - 1, H, sH, off);
-    const int xx = map_coord<PAD>(x0 + sx - 1, W, sW, off);
-    bf16x8 v;
-    if (yy < 0 || xx < 0) {
+  // ---- stage 6 rows x 66 pixels x C in batches of up to STAGE_BATCH
+  // vectors per thread: a batch's loads are all issued before its LDS
+  // writes, so a thread keeps that many 16-byte loads in flight ----
+  {
+    const __hip_bfloat16* x_n = x + (int64_t)n * sH * sW * CPIX;
+    StageIdx<CV> si(tid), sj(tid);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = (__bf16)0.0f;
-    } else {
-      v = *reinterpret_cast<const bf16x8*>(
-          x + x_n + ((int64_t)yy * sW + xx) * C + cv * 8);
+    for (int b0 = 0; b0 < NIT; b0 += STAGE_BATCH) {
+      bf16x8 v[STAGE_BATCH];
+#pragma unroll
+      for (int it = 0; it < STAGE_BATCH; ++it) {
+        if (b0 + it >= NIT) break;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[it][e] = (__bf16)0.0f;
+        if (si.row < STAGE_H) {
+          const int yy = map_coord<PAD>(y0 + si.row - 1, H, sH, off);
+          const int xx = map_coord<PAD>(x0 + si.x - 1, W, sW, off);
+          if (yy >= 0 && xx >= 0) {
+            const __hip_bfloat16* src =
+                x_n + ((int64_t)yy * sW + xx) * CPIX + si.cv * 8;
+            if (CIN4) {
+              using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
+              const bf16x4 h = *reinterpret_cast<const bf16x4*>(src);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) v[it][e] = h[e];
+            } else {
+              v[it] = *reinterpret_cast<const bf16x8*>(src);
+            }
+          }
+        }
+        si.next();
+      }
+#pragma unroll
+      for (int it = 0; it < STAGE_BATCH; ++it) {
+        if (b0 + it >= NIT) break;
+        if (sj.row < STAGE_H)
+          s_in[sj.cv * CB_PITCH + sj.row * ROW_PITCH + sj.x] = v[it];
+        sj.next();
+      }
     }
-    *reinterpret_cast<bf16x8*>(s_in + (i * 8)) = v;
   }
   __syncthreads();
 
@@ -97,91 +203,196 @@ conv3x3_fwd_kernel(const __hip_bfloat16* __restrict__ x,  // (N,sH,sW,C)
   const int wave = tid >> 6;
   const int lane = tid & 63;
   const int px_base = wave * 16;            // this wave's 16 pixels
-  const int i_row = lane & 15;              // A row / output pixel offset
-  const int seg_in_chunk = lane >> 4;       // 0..3
+  // a wave whose 16 pixels all lie past the image edge has nothing to
+  // compute or store (wave-uniform; no barrier follows)
+  if (x0 + px_base >= W) return;
+  const int p = lane & 15;                  // B col / output pixel offset
+  const int g = lane >> 4;                  // segment within a chunk
 
-  const int nseg = 9 * Cv;                  // segments of 8 k
-  const int nchunks = (nseg + 3) / 4;       // 32-wide K chunks
-  const int nK = (K + 15) / 16;             // 16-wide N chunks (K zero-padded)
-
-  f32x4 acc[4];                             // up to K=64 held at once
-  const int nK_held = nK <= 4 ? nK : 4;
-
-  for (int row = 0; row < TILE_H; ++row) {
-    const int y = y0 + row;
-    if (y >= H) break;
-    for (int nc0 = 0; nc0 < nK; nc0 += nK_held) {
+  f32x4 acc[TILE_H][NK];
 #pragma unroll
-      for (int a = 0; a < 4; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int r = 0; r < TILE_H; ++r)
+#pragma unroll
+    for (int a = 0; a < NK; ++a) acc[r][a] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-      for (int kc = 0; kc < nchunks; ++kc) {
-        const int seg = kc * 4 + seg_in_chunk;
-        bf16x8 afrag;
-        if (seg < nseg) {
-          const int cb = seg / 9;
-          const int tap = seg - cb * 9;
-          const int dy = tap / 3, dx = tap - dy * 3;
-          // staged coords: row (row + dy), x (px_base + i_row) + dx
-          const int sx = px_base + i_row + dx;  // 0..65 (+2 from taps)
-          afrag = *reinterpret_cast<const bf16x8*>(
-              s_in + (((row + dy) * STAGE_W + sx) * Cv + cb) * 8);
-        } else {
+  const bf16x8* s_lane = s_in + px_base + p;
+  const bf16x8* w_lane = wp + lane;
+
 #pragma unroll
-          for (int e = 0; e < 8; ++e) afrag[e] = (__bf16)0.0f;
-        }
+  for (int kc = 0; kc < NCH; ++kc) {
+    // constants after unrolling: three selects per chunk
+    const int o = g == 0 ? seg_vec_off(kc * 4 + 0, NSEG)
+                : g == 1 ? seg_vec_off(kc * 4 + 1, NSEG)
+                : g == 2 ? seg_vec_off(kc * 4 + 2, NSEG)
+                         : seg_vec_off(kc * 4 + 3, NSEG);
+    bf16x8 wf[NK];
 #pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          if (a < nK_held && nc0 + a < nK) {
-            const bf16x8 bfrag = *reinterpret_cast<const bf16x8*>(
-                wp + (((int64_t)(nc0 + a) * nchunks + kc) * 64 + lane) * 8);
-            acc[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag, bfrag,
-                                                             acc[a], 0, 0, 0);
-          }
+    for (int a = 0; a < NK; ++a) wf[a] = w_lane[(a * NCH + kc) * 64];
+#pragma unroll
+    for (int r = 0; r < TILE_H; ++r) {
+      bf16x8 b = s_lane[o + r * ROW_PITCH];
+      if (kc * 4 + 3 >= NSEG) {  // the zero-padded tail of the K-dim
+        if (kc * 4 + g >= NSEG) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) b[e] = (__bf16)0.0f;
         }
       }
+#pragma unroll
+      for (int a = 0; a < NK; ++a)
+        acc[r][a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[a], b,
+                                                            acc[r][a], 0, 0, 0);
+    }
+  }
 
-      // ---- epilogue: bias + store ----
-      const int j = lane & 15;               // output channel offset
+  // ---- epilogue: bias in fp32, one rounding, 8-byte stores ----
+  const int pix = x0 + px_base + p;
+  if (pix >= W) return;
 #pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        if (a < nK_held && nc0 + a < nK) {
-          const int kout = (nc0 + a) * 16 + j;
-          const float b = (bias && kout < K) ? bias[kout] : 0.0f;
+  for (int a = 0; a < NK; ++a) {
+    const int kout = k0 + a * 16 + g * 4;   // this lane's 4 channels
+    if (kout >= K) continue;
+    float b4[4] = {0.f, 0.f, 0.f, 0.f};
+    if (bias) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int pix = x0 + px_base + (lane >> 4) * 4 + r;
-            if (pix < W && kout < K) {
-              out[((int64_t)n * H + y) * W * K + (int64_t)pix * K + kout] =
-                  (__hip_bfloat16)(acc[a][r] + b);
-            }
-          }
-        }
+      for (int r = 0; r < 4; ++r)
+        if (kout + r < K) b4[r] = bias[kout + r];
+    }
+#pragma unroll
+    for (int r = 0; r < TILE_H; ++r) {
+      const int y = y0 + r;
+      if (y >= H) break;
+      __hip_bfloat16* dst = out + (((int64_t)n * H + y) * W + pix) * K + kout;
+      __hip_bfloat16 h[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        h[c] = (__hip_bfloat16)(acc[r][a][c] + b4[c]);
+      if (KVEC) {
+        uint2 u;
+        u.x = (uint32_t)__bfloat16_as_ushort(h[0]) |
+              ((uint32_t)__bfloat16_as_ushort(h[1]) << 16);
+        u.y = (uint32_t)__bfloat16_as_ushort(h[2]) |
+              ((uint32_t)__bfloat16_as_ushort(h[3]) << 16);
+        *reinterpret_cast<uint2*>(dst) = u;
+      } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (kout + c < K) dst[c] = h[c];
       }
     }
   }
 }
 
+template <int PAD, int CV, int NK, bool CIN4>
+void launch(const void* x, const void* wp, const float* bias, void* out,
+            int N, int H, int W, int K, int k0, int sH, int sW, int off,
+            hipStream_t stream) {
+  constexpr int NCH = (9 * CV + 3) / 4;
+  const dim3 grid((W + TILE_W - 1) / TILE_W, (H + TILE_H - 1) / TILE_H, N);
+  const size_t lds = (size_t)CV * CB_PITCH * sizeof(bf16x8);
+  // weights of output-channel tile k0/16 onwards
+  const bf16x8* wk =
+      reinterpret_cast<const bf16x8*>(wp) + (size_t)(k0 / 16) * NCH * 64;
+  if (K % 4 == 0)
+    hipLaunchKernelGGL((conv3x3_fwd_kernel<PAD, CV, NK, CIN4, true>), grid,
+                       dim3(kBlock), lds, stream,
+                       reinterpret_cast<const __hip_bfloat16*>(x), wk, bias,
+                       reinterpret_cast<__hip_bfloat16*>(out), H, W, K, k0,
+                       sH, sW, off);
+  else
+    hipLaunchKernelGGL((conv3x3_fwd_kernel<PAD, CV, NK, CIN4, false>), grid,
+                       dim3(kBlock), lds, stream,
+                       reinterpret_cast<const __hip_bfloat16*>(x), wk, bias,
+                       reinterpret_cast<__hip_bfloat16*>(out), H, W, K, k0,
+                       sH, sW, off);
+}
+
+template <int PAD, int CV, bool CIN4>
+void launch_nk(int nk, const void* x, const void* wp, const float* bias,
+               void* out, int N, int H, int W, int K, int k0, int sH, int sW,
+               int off, hipStream_t s) {
+  switch (nk) {
+    case 1: launch<PAD, CV, 1, CIN4>(x, wp, bias, out, N, H, W, K, k0, sH, sW, off, s); break;
+    case 2: launch<PAD, CV, 2, CIN4>(x, wp, bias, out, N, H, W, K, k0, sH, sW, off, s); break;
+    case 3: launch<PAD, CV, 3, CIN4>(x, wp, bias, out, N, H, W, K, k0, sH, sW, off, s); break;
+    default: launch<PAD, CV, 4, CIN4>(x, wp, bias, out, N, H, W, K, k0, sH, sW, off, s); break;
+  }
+}
+
+template <int PAD>
+bool launch_cv(int cv, bool cin4, int nk, const void* x, const void* wp,
+               const float* bias, void* out, int N, int H, int W, int K,
+               int k0, int sH, int sW, int off, hipStream_t s) {
+  if (cin4) {
+    if (PAD != PAD_ZERO || cv != 1) return false;
+    launch_nk<PAD_ZERO, 1, true>(nk, x, wp, bias, out, N, H, W, K, k0, sH, sW, off, s);
+    return true;
+  }
+  switch (cv) {
+#define MINE_CONV_CV(V)                                                       \
+    case V: launch_nk<PAD, V, false>(nk, x, wp, bias, out, N, H, W, K, k0,   \
+                                     sH, sW, off, s); return true;
+    MINE_CONV_CV(1) MINE_CONV_CV(2) MINE_CONV_CV(3) MINE_CONV_CV(4)
+    MINE_CONV_CV(5) MINE_CONV_CV(6) MINE_CONV_CV(7) MINE_CONV_CV(8)
+#undef MINE_CONV_CV
+  }
+  return false;
+}
+
 }  // namespace
 
-extern "C" void mine_conv3x3_fwd(const void* x, const void* wp,
-                                 const float* bias, void* out, int N, int H,
-                                 int W, int C, int K, int pad_mode,
-                                 int src_h, int src_w, int off,
-                                 hipStream_t stream) {
-  const dim3 grid((W + TILE_W - 1) / TILE_W, (H + TILE_H - 1) / TILE_H, N);
-  const size_t lds = STAGE_H * STAGE_W * C * sizeof(__hip_bfloat16);
-  if (pad_mode == PAD_REFLECT)
-    hipLaunchKernelGGL(conv3x3_fwd_kernel<PAD_REFLECT>, grid, dim3(kBlock),
-                       lds, stream,
-                       reinterpret_cast<const __hip_bfloat16*>(x),
-                       reinterpret_cast<const __hip_bfloat16*>(wp), bias,
-                       reinterpret_cast<__hip_bfloat16*>(out), H, W, C, K,
-                       src_h, src_w, off);
+// C = logical input channels (multiple of 8, <= 64); c_mem = channels
+// per pixel in memory: C, or 4 with C == 8 in zero-embed mode. Output
+// channels beyond 64 run as further launches over the same input.
+// Returns 0, or -1 when no kernel is instantiated for the shape.
+extern "C" int mine_conv3x3_fwd(const void* x, const void* wp,
+                                const float* bias, void* out, int N, int H,
+                                int W, int C, int c_mem, int K, int pad_mode,
+                                int src_h, int src_w, int off,
+                                hipStream_t stream) {
+  if (C % 8 || C < 8 || C > 64 || K < 1) return -1;
+  const bool cin4 = c_mem != C;
+  if (cin4 && !(c_mem == 4 && C == 8)) return -1;
+  for (int k0 = 0; k0 < K; k0 += 64) {
+    const int nk = (((K - k0) < 64 ? (K - k0) : 64) + 15) / 16;
+    const bool ok =
+        pad_mode == PAD_REFLECT
+            ? launch_cv<PAD_REFLECT>(C / 8, cin4, nk, x, wp, bias, out, N, H,
+                                     W, K, k0, src_h, src_w, off, stream)
+            : launch_cv<PAD_ZERO>(C / 8, cin4, nk, x, wp, bias, out, N, H, W,
+                                  K, k0, src_h, src_w, off, stream);
+    if (!ok) return -1;
+  }
+  return 0;
+}
+
+// Gather a (K,C,3,3) weight into MFMA fragment order in one launch:
+// out[i] = bf16(w[lut[i]]), or 0 where lut[i] is the one-past-the-end
+// pad slot. fp32 -> bf16 rounds to nearest even, as torch's cast does.
+namespace {
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+conv3x3_pack_kernel(const T* __restrict__ w, const int64_t* __restrict__ lut,
+                    __hip_bfloat16* __restrict__ out, int64_t n_out,
+                    int64_t n_w) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n_out) return;
+  const int64_t j = lut[i];
+  out[i] = (j >= 0 && j < n_w) ? (__hip_bfloat16)(float)w[j]
+                               : (__hip_bfloat16)0.0f;
+}
+}  // namespace
+
+extern "C" void mine_conv3x3_pack(const void* w, int is_bf16,
+                                  const int64_t* lut, void* out,
+                                  int64_t n_out, int64_t n_w,
+                                  hipStream_t stream) {
+  const dim3 grid((unsigned)((n_out + kBlock - 1) / kBlock));
+  if (is_bf16)
+    hipLaunchKernelGGL(conv3x3_pack_kernel<__hip_bfloat16>, grid, dim3(kBlock),
+                       0, stream, reinterpret_cast<const __hip_bfloat16*>(w),
+                       lut, reinterpret_cast<__hip_bfloat16*>(out), n_out, n_w);
   else
-    hipLaunchKernelGGL(conv3x3_fwd_kernel<PAD_ZERO>, grid, dim3(kBlock),
-                       lds, stream,
-                       reinterpret_cast<const __hip_bfloat16*>(x),
-                       reinterpret_cast<const __hip_bfloat16*>(wp), bias,
-                       reinterpret_cast<__hip_bfloat16*>(out), H, W, C, K,
-                       src_h, src_w, off);
+    hipLaunchKernelGGL(conv3x3_pack_kernel<float>, grid, dim3(kBlock), 0,
+                       stream, reinterpret_cast<const float*>(w), lut,
+                       reinterpret_cast<__hip_bfloat16*>(out), n_out, n_w);
 }
