@@ -7,8 +7,9 @@ layers.py:106-138) on hand-written v_mfma_f32_16x16x32_bf16 tiles.
 Forward runs the hand-written v_mfma_f32_16x16x32_bf16 kernel
 (ops/csrc/conv_kernels.hip) with the pad folded into the LDS stage — no
 padded tensor is ever materialized. Backward is hand-written too:
-dW on the split-K MFMA wrw kernel (ops/csrc/wrw_kernels.hip, reflect
-staged in LDS, fp32 atomics into the K x 9C output) and dX by driving
+dW (and the bias gradient, in the same pass) on the MFMA wrw kernel
+(ops/csrc/wrw_kernels.hip, reflect staged in LDS, per-slab partials
+summed in a fixed order) and dX by driving
 the SAME fwd kernel in zero-embed mode, its weights read transposed and
 flipped through the pack LUT, plus the atomic-free reflect fold (identity proven in
 tests/test_properties.py). MINE_CONV_BWD=miopen restores the round-1
@@ -120,6 +121,9 @@ def pack_weights_bwd(w: torch.Tensor) -> torch.Tensor:
 def bias_grad(gy: torch.Tensor) -> torch.Tensor:
     """Per-channel sum of a (B,K,H,W) channels_last gradient, fp32.
 
+    The fused conv's backward gets its bias gradient from the wrw kernel
+    (ext.conv3x3_wrw_bias); this is the stand-alone form.
+
     On the GPU in bf16 this is the BN statistics kernel's sum half: it
     reads the bf16 gradient once at stream rate and makes no fp32 copy.
     Like every BN statistic it combines per-block partials with fp32
@@ -195,13 +199,16 @@ class _Conv3x3ReflFn(torch.autograd.Function):
         gy = gy.contiguous(memory_format=torch.channels_last)
         if _bwd_mode() == "hip":
             ext = get_extension(required=True)
-            # dW on the split-K MFMA wrw kernel (fp32 accumulate); reads
-            # the unpadded bf16 x with the reflect staged in LDS
-            gw = ext.conv3x3_wrw(
-                xs.permute(0, 2, 3, 1).reshape(-1),
-                gy.permute(0, 2, 3, 1).reshape(-1),
-                B, H, W, C, K).view(K, C, 3, 3)
-            gb = bias_grad(gy) if ctx.has_bias else None
+            # dW on the MFMA wrw kernel (fp32 accumulate); reads the
+            # unpadded bf16 x with the reflect staged in LDS. The bias
+            # gradient comes out of the same pass over gy.
+            x_flat = xs.permute(0, 2, 3, 1).reshape(-1)
+            gy_flat = gy.permute(0, 2, 3, 1).reshape(-1)
+            if ctx.has_bias:
+                gw, gb = ext.conv3x3_wrw_bias(x_flat, gy_flat, B, H, W, C, K)
+            else:
+                gw = ext.conv3x3_wrw(x_flat, gy_flat, B, H, W, C, K)
+                gb = None
             # dX: the SAME MFMA fwd kernel in zero-embed mode (weights
             # gathered transposed + flipped) + the atomic-free reflect fold
             gx = conv3x3_bwd_data(gy, w)

@@ -56,8 +56,9 @@ int mine_conv3x3_fwd(const void*, const void*, const float*, void*, int, int,
                      int, int, int, int, int, int, int, int, hipStream_t);
 void mine_conv3x3_pack(const void*, int, const int64_t*, void*, int64_t,
                        int64_t, hipStream_t);
-void mine_conv3x3_wrw(const void*, const void*, float*, int, int, int, int,
-                      int, hipStream_t);
+void mine_conv3x3_wrw_plan(int, int, int64_t, int, int*, int*, int64_t*);
+int mine_conv3x3_wrw(const void*, const void*, float*, float*, float*, int,
+                     int, int, int, int, int, int, hipStream_t);
 void mine_mpi_head_fwd_f32(const void*, float*, int64_t, int, hipStream_t);
 void mine_mpi_head_fwd_bf16(const void*, float*, int64_t, int, hipStream_t);
 void mine_mpi_head_bwd_f32(const void*, const float*, void*, int64_t, int,
@@ -432,20 +433,65 @@ at::Tensor conv3x3_pack(at::Tensor w_flat, at::Tensor lut) {
   return out;
 }
 
-// Split-K MFMA weight gradient (see wrw_kernels.hip);
-// returns dW fp32 (K, C, 3, 3). Flat NHWC bf16 inputs.
-at::Tensor conv3x3_wrw(at::Tensor x_flat, at::Tensor gy_flat, int64_t N,
-                       int64_t H, int64_t W, int64_t C, int64_t K) {
-  TORCH_CHECK(x_flat.is_cuda() && x_flat.is_contiguous() &&
-              gy_flat.is_contiguous());
+// Weight (and bias) gradient of the fused reflect-pad 3x3 conv (see
+// wrw_kernels.hip). Flat NHWC bf16 inputs; returns dW fp32 (K, C, 3, 3)
+// and, with want_bias, db fp32 (K). Every workgroup writes its partial
+// to a workspace and a second kernel sums them in a fixed order, so the
+// result is bitwise reproducible. max_slabs caps the number of pixel
+// slabs (0 = automatic).
+static std::tuple<at::Tensor, at::Tensor> wrw_impl(
+    at::Tensor x_flat, at::Tensor gy_flat, int64_t N, int64_t H, int64_t W,
+    int64_t C, int64_t K, bool want_bias, int64_t max_slabs) {
+  TORCH_CHECK(x_flat.is_cuda() && gy_flat.is_cuda() &&
+              x_flat.is_contiguous() && gy_flat.is_contiguous());
   TORCH_CHECK(x_flat.scalar_type() == at::kBFloat16 &&
               gy_flat.scalar_type() == at::kBFloat16);
-  TORCH_CHECK(C % 16 == 0 && W >= 2);
-  auto dw = at::zeros({K, C, 3, 3}, x_flat.options().dtype(at::kFloat));
-  mine_conv3x3_wrw(x_flat.data_ptr(), gy_flat.data_ptr(),
-                   dw.data_ptr<float>(), (int)N, (int)H, (int)W, (int)C,
-                   (int)K, stream());
-  return dw;
+  TORCH_CHECK(C % 16 == 0 && C >= 16 && C <= 64,
+              "conv3x3_wrw: C must be 16, 32, 48 or 64, got ", C);
+  TORCH_CHECK(K >= 1 && W >= 2 && H >= 2 && N >= 1 && max_slabs >= 0);
+  TORCH_CHECK(N * H < (1 << 30) && W < (1 << 24));
+  TORCH_CHECK(x_flat.numel() == N * H * W * C &&
+              gy_flat.numel() == N * H * W * K);
+  // the kernel stages gy in 8-byte (K = 4) or 16-byte pieces; any other
+  // channel count is zero-padded to a multiple of 8 first
+  int64_t Kmem = K;
+  if (K != 4 && K % 8 != 0) {
+    Kmem = (K + 7) / 8 * 8;
+    gy_flat = at::constant_pad_nd(gy_flat.view({N * H * W, K}),
+                                  {0, Kmem - K}).reshape({-1});
+  }
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x_flat.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(gy_flat.data_ptr()) % 16 == 0,
+              "conv3x3_wrw: inputs must be 16-byte aligned");
+  int slabs = 0, nkb = 0;
+  int64_t ws_floats = 0;
+  mine_conv3x3_wrw_plan((int)C, (int)Kmem, N * H, (int)max_slabs, &slabs,
+                        &nkb, &ws_floats);
+  auto fopt = x_flat.options().dtype(at::kFloat);
+  auto ws = at::empty({ws_floats}, fopt);
+  auto dw = at::empty({K, C, 3, 3}, fopt);
+  auto db = want_bias ? at::empty({K}, fopt) : at::Tensor();
+  const int rc = mine_conv3x3_wrw(
+      x_flat.data_ptr(), gy_flat.data_ptr(), ws.data_ptr<float>(),
+      dw.data_ptr<float>(), want_bias ? db.data_ptr<float>() : nullptr,
+      (int)N, (int)H, (int)W, (int)C, (int)Kmem, (int)K, slabs, stream());
+  TORCH_CHECK(rc != -2, "conv3x3_wrw: kernel launch failed for C=", C,
+              " K=", K);
+  TORCH_CHECK(rc == 0, "conv3x3_wrw: no kernel for C=", C, " K=", K);
+  return {dw, db};
+}
+
+at::Tensor conv3x3_wrw(at::Tensor x_flat, at::Tensor gy_flat, int64_t N,
+                       int64_t H, int64_t W, int64_t C, int64_t K,
+                       int64_t max_slabs) {
+  return std::get<0>(
+      wrw_impl(x_flat, gy_flat, N, H, W, C, K, false, max_slabs));
+}
+
+std::tuple<at::Tensor, at::Tensor> conv3x3_wrw_bias(
+    at::Tensor x_flat, at::Tensor gy_flat, int64_t N, int64_t H, int64_t W,
+    int64_t C, int64_t K, int64_t max_slabs) {
+  return wrw_impl(x_flat, gy_flat, N, H, W, C, K, true, max_slabs);
 }
 
 // fused MPI head over a flat (N,4) view; out is fp32 (N,4)
@@ -732,5 +778,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("conv3x3_pack", &conv3x3_pack,
           "gather a conv weight into MFMA fragment order (bf16)");
   mod.def("conv3x3_wrw", &conv3x3_wrw,
-          "EXPERIMENTAL split-K MFMA weight gradient (unwired)");
+          "reflect-pad 3x3 conv weight gradient, fp32 (K, C, 3, 3)",
+          py::arg("x_flat"), py::arg("gy_flat"), py::arg("N"), py::arg("H"),
+          py::arg("W"), py::arg("C"), py::arg("K"), py::arg("max_slabs") = 0);
+  mod.def("conv3x3_wrw_bias", &conv3x3_wrw_bias,
+          "weight and bias gradient in one pass -> (dw, db)",
+          py::arg("x_flat"), py::arg("gy_flat"), py::arg("N"), py::arg("H"),
+          py::arg("W"), py::arg("C"), py::arg("K"), py::arg("max_slabs") = 0);
 }
