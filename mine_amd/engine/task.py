@@ -95,6 +95,20 @@ class SynthesisTask:
             torch.backends.cudnn.benchmark = bool(
                 config.get("training.miopen_benchmark", False))
 
+        # Deterministic mode (ops/backend.py): order-fixed BN and igemm
+        # reductions, every reflect conv on the in-tree kernels (a library
+        # weight-gradient kernel gives no ordering guarantee), and the
+        # library's own deterministic flag for whatever still falls back.
+        # Only ever switched ON here: MINE_DETERMINISTIC=1 stays in force
+        # when the key is false.
+        self.deterministic = bool(config.get("training.deterministic", False))
+        if self.deterministic:
+            from mine_amd.ops.backend import set_deterministic
+            from mine_amd.ops.conv import set_force_igemm
+            set_deterministic(True)
+            set_force_igemm(True)
+            torch.backends.cudnn.deterministic = True
+
         amp = str(config.get("training.amp_dtype", "bf16")).lower()
         self.amp_dtype = {"bf16": torch.bfloat16, "fp16": torch.float16,
                           "fp32": None, "float32": None}[amp]
@@ -683,7 +697,7 @@ class SynthesisTask:
             return True
         except Exception as exc:  # pragma: no cover - depends on runtime
             from mine_amd.ops.conv import set_force_igemm
-            set_force_igemm(False)
+            set_force_igemm(self.deterministic)
             self._graph_error = f"{type(exc).__name__}: {exc}"
             if self.logger:
                 self.logger.warning("hipGraph capture failed (%s); "

@@ -30,6 +30,11 @@ from mine_amd.ops.torch_ref import (  # noqa: F401
     volume_composite,
     weighted_sum_mpi,
 )
+from mine_amd.ops.backend import (  # noqa: F401
+    deterministic,
+    is_deterministic,
+    set_deterministic,
+)
 from mine_amd.ops.renderer import render_src_view, render_tgt_view  # noqa: F401
 from mine_amd.ops.ssim import ssim  # noqa: F401
 from mine_amd.ops.losses import (  # noqa: F401

@@ -9,6 +9,7 @@ back to eager PyTorch.
 """
 from __future__ import annotations
 
+import contextlib
 import importlib
 from typing import Optional
 
@@ -36,3 +37,49 @@ def get_extension(required: bool = False):
 
 def has_extension() -> bool:
     return get_extension(required=False) is not None
+
+
+# ---------------------------------------------------------------------------
+# Deterministic mode (off by default).
+#
+# When on, every reduction inside the network — the BN statistics and
+# backward reductions, `bias_grad`, the igemm split-K forward / data
+# gradient and the igemm weight gradient — combines its partial sums in
+# an order that depends only on the shapes (per-block / per-slice
+# partials in a workspace, summed by a finishing kernel) instead of with
+# fp32 atomics. The forward becomes bit-reproducible, and so does the
+# backward given the same upstream gradient. Not covered: the renderer's
+# warp backward, the SSIM / smoothness loss scalars and the RCCL
+# all-reduce order (docs/NEXT.md section 7).
+#
+# The initial value is read lazily from MINE_DETERMINISTIC=1, the same
+# convention as MINE_TGT_BWD / MINE_CONV_BWD. The autograd functions read
+# the mode once in forward and keep it for their backward.
+# ---------------------------------------------------------------------------
+
+_DETERMINISTIC: Optional[bool] = None  # lazy: MINE_DETERMINISTIC
+
+
+def is_deterministic() -> bool:
+    global _DETERMINISTIC
+    if _DETERMINISTIC is None:
+        import os
+        _DETERMINISTIC = os.environ.get("MINE_DETERMINISTIC", "0") == "1"
+    return _DETERMINISTIC
+
+
+def set_deterministic(enabled: bool) -> None:
+    global _DETERMINISTIC
+    _DETERMINISTIC = bool(enabled)
+
+
+@contextlib.contextmanager
+def deterministic(enabled: bool = True):
+    """Run the body in (or, with enabled=False, out of) deterministic
+    mode; the previous value is restored on exit."""
+    prev = is_deterministic()
+    set_deterministic(enabled)
+    try:
+        yield
+    finally:
+        set_deterministic(prev)

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from mine_amd.ops.backend import get_extension
+from mine_amd.ops.backend import get_extension, is_deterministic
 
 _ACT = {"none": 0, "relu": 1, "lrelu": 2, "elu": 3, "add_relu": 4}
 
@@ -35,6 +35,9 @@ class _BNActFn(torch.autograd.Function):
                            gamma, beta, M, C, act)
         ctx.save_for_backward(x_flat, res_flat, mean, invstd, gamma, beta)
         ctx.geom = (M, C, act, sync)
+        # read once here: a graph built in deterministic mode stays
+        # deterministic when .backward() runs after the mode is left
+        ctx.det = is_deterministic()
         return y
 
     @staticmethod
@@ -44,7 +47,7 @@ class _BNActFn(torch.autograd.Function):
         M, C, act, sync = ctx.geom
         gy = gy.contiguous()
         red = ext.bn_act_bwd_reduce(x_flat, res_flat, gy, mean, invstd,
-                                    gamma, beta, M, C, act)
+                                    gamma, beta, M, C, act, 0, ctx.det)
         # SyncBN backward: dx needs the GLOBAL (dbeta, dgamma) sums and the
         # global batch count; the returned parameter grads stay LOCAL (DDP
         # averages them afterwards, matching torch SyncBatchNorm + DDP).
@@ -72,12 +75,14 @@ class _JoinStatsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y_dec, y_base, bias, B, S):
         ext = get_extension(required=True)
+        det = is_deterministic()
         _, K, H, W = y_dec.shape
         x_flat, sums = ext.bn_join_stats(
             y_dec.permute(0, 2, 3, 1).reshape(-1),
             y_base.permute(0, 2, 3, 1).reshape(-1),
-            bias.contiguous(), B, S, H * W, K)
+            bias.contiguous(), B, S, H * W, K, 0, det)
         ctx.geom = (B, S, H, W, K)
+        ctx.det = det  # backward below sums with torch ops only
         ctx.mark_non_differentiable(sums)
         return x_flat.view(B * S, H, W, K).permute(0, 3, 1, 2), sums
 
@@ -182,7 +187,8 @@ class FusedBNAct(nn.BatchNorm2d):
             empty = torch.empty(0, device=x.device, dtype=torch.float32)
             if do_sync:
                 if sums is None:
-                    sums = ext.bn_sums(x_flat.detach(), M, C)
+                    sums = ext.bn_sums(x_flat.detach(), M, C, 0,
+                                       is_deterministic())
                 torch.distributed.all_reduce(sums)
                 Mg = M * torch.distributed.get_world_size()
                 mean = sums[:C] / Mg
@@ -200,7 +206,7 @@ class FusedBNAct(nn.BatchNorm2d):
                     x_flat.detach(), M, C,
                     self.running_mean if track else empty,
                     self.running_var if track else empty,
-                    self.eps, mom)
+                    self.eps, mom, 0, is_deterministic())
             else:
                 mean, invstd = ext.bn_finalize(
                     sums, M, C,

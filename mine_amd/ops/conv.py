@@ -30,7 +30,7 @@ from typing import Dict, Tuple
 import torch
 import torch.nn.functional as F
 
-from mine_amd.ops.backend import get_extension
+from mine_amd.ops.backend import get_extension, is_deterministic
 
 _LUT_CACHE: Dict[Tuple[int, int, int, torch.device], torch.Tensor] = {}
 _BWD_LUT_CACHE: Dict[Tuple[int, int, torch.device], torch.Tensor] = {}
@@ -127,7 +127,8 @@ def bias_grad(gy: torch.Tensor) -> torch.Tensor:
     On the GPU in bf16 this is the BN statistics kernel's sum half: it
     reads the bf16 gradient once at stream rate and makes no fp32 copy.
     Like every BN statistic it combines per-block partials with fp32
-    atomics, so the last bits depend on the order the blocks finish in.
+    atomics, so the last bits depend on the order the blocks finish in;
+    in deterministic mode (ops.backend) it takes the order-fixed kernels.
     A 4-channel gradient is summed as (M/2, 8) and its halves added.
     """
     B, K, H, W = gy.shape
@@ -137,9 +138,9 @@ def bias_grad(gy: torch.Tensor) -> torch.Tensor:
         ext = get_extension(required=True)
         flat = gy.permute(0, 2, 3, 1).reshape(-1)
         if K % 8 == 0:
-            return ext.bn_sums(flat, M, K, 0)[:K]
+            return ext.bn_sums(flat, M, K, 0, is_deterministic())[:K]
         if K == 4 and M % 2 == 0:
-            s = ext.bn_sums(flat, M // 2, 8, 0)
+            s = ext.bn_sums(flat, M // 2, 8, 0, is_deterministic())
             return s[:4] + s[4:8]
     return gy.float().sum((0, 2, 3))
 
@@ -151,7 +152,9 @@ _FORCE_IGEMM = False  # graph capture: no library convs (workspace allocs)
 def set_force_igemm(v: bool) -> None:
     """Route EVERY reflect conv through the hand-written kernels — the
     library path allocates find/workspace memory per call, which breaks
-    hipGraph capture. Set by SynthesisTask.enable_graph_step."""
+    hipGraph capture, and its weight-gradient kernels give no ordering
+    guarantee. Set by SynthesisTask.enable_graph_step and by
+    training.deterministic."""
     global _FORCE_IGEMM
     _FORCE_IGEMM = bool(v)
 
@@ -251,10 +254,14 @@ def conv3x3_reflect(x: torch.Tensor, w: torch.Tensor,
     if usable:
         return _Conv3x3ReflFn.apply(x, w, bias)
     if x.is_cuda and x.dtype == torch.bfloat16 and (
-            _FORCE_IGEMM or x.numel() * 2 <= 1 << 25):
+            _FORCE_IGEMM or is_deterministic()
+            or x.numel() * 2 <= 1 << 25):
         # small (L2/L3-resident) narrow-image shapes, e.g. the 256-ch
         # decoder block at H/16: the general igemm family (its direct
-        # loads re-read x per tap, so gate on cache residency)
+        # loads re-read x per tap, so gate on cache residency).
+        # Deterministic mode sends the rest here too (the C=128 wide
+        # blocks): a library weight-gradient kernel gives no ordering
+        # guarantee.
         from mine_amd.ops.conv_general import conv2d_mfma
         return conv2d_mfma(x, w, bias, reflect=True)
     from mine_amd.ops.pad import reflection_pad2d

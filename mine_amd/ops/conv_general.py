@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from mine_amd.ops.backend import get_extension
+from mine_amd.ops.backend import get_extension, is_deterministic
 
 _LUT: Dict[Tuple, torch.Tensor] = {}
 
@@ -102,13 +102,16 @@ class _ConvIgemmFn(torch.autograd.Function):
             Q = (Ws + 2 * pad - S) // stride + 1
         wp = pack_weights_general(w)
         M = B * P * Q
+        # read once: backward uses the mode the graph was built in
+        det = is_deterministic()
         out = ext.conv_igemm_fwd(
             x.permute(0, 2, 3, 1).reshape(-1), wp,
             bias.float() if bias is not None else
             torch.empty(0, device=x.device, dtype=torch.float32),
             M, P, Q, K, Hs, Ws, Cp, R, S,
-            stride, 1, -pad, 1, 1 if reflect else 0)
+            stride, 1, -pad, 1, 1 if reflect else 0, det)
         ctx.save_for_backward(x, w)
+        ctx.det = det
         ctx.geom = (B, C, Cp, Hs, Ws, K, R, S, P, Q, stride, pad, reflect)
         ctx.has_bias = bias is not None
         return out.view(B, P, Q, K).permute(0, 3, 1, 2)
@@ -137,7 +140,7 @@ class _ConvIgemmFn(torch.autograd.Function):
             # wrw maps OUT pixels through the forward tap coordinates
             dw = ext.conv_igemm_wrw(
                 x_flat, gy_flat, B * P * Q, P, Q, K, Hs, Ws, Cp, R, S,
-                stride, 1, -pad, 1, 1 if reflect else 0)
+                stride, 1, -pad, 1, 1 if reflect else 0, ctx.det)
             gw = dw.view(K, Cp, R, S)[:, :C] if Cp != C \
                 else dw.view(K, C, R, S)
             gw = gw.to(w.dtype)
@@ -151,13 +154,13 @@ class _ConvIgemmFn(torch.autograd.Function):
                 Hp, Wp_ = Hs + 2 * pad, Ws + 2 * pad
                 gxp = ext.conv_igemm_fwd(
                     gy_flat_p, wtp, empty, B * Hp * Wp_, Hp, Wp_, Cp,
-                    P, Q, Kp, R, S, 1, -1, 0, 1, 0)
+                    P, Q, Kp, R, S, 1, -1, 0, 1, 0, ctx.det)
                 gx = ext.reflect_pad_bwd(gxp, B, Hs, Ws, Cp, pad)
                 gx = gx.view(B, Hs, Ws, Cp).permute(0, 3, 1, 2)
             else:
                 gxf = ext.conv_igemm_fwd(
                     gy_flat_p, wtp, empty, B * Hs * Ws, Hs, Ws, Cp,
-                    P, Q, Kp, R, S, 1, -1, pad, stride, 0)
+                    P, Q, Kp, R, S, 1, -1, pad, stride, 0, ctx.det)
                 gx = gxf.view(B, Hs, Ws, Cp).permute(0, 3, 1, 2)
             if Cp != C:
                 gx = gx[:, :C]
@@ -171,6 +174,12 @@ def conv2d_mfma(x: torch.Tensor, w: torch.Tensor,
     fast-path conditions don't hold. reflect=True means
     ReflectionPad((R-1)/2) + unpadded conv (stride must be 1)."""
     K, C, R, S = w.shape
+    if x.is_cuda and not w.is_contiguous() and is_deterministic():
+        # module.to(memory_format=channels_last) leaves 3x3 / 7x7 weights
+        # channels_last, which fails `usable` below and sends the conv to
+        # the library (and a reflect conv through eager F.pad, whose
+        # backward sums with atomics). Deterministic mode keeps it here.
+        w = w.contiguous()
     if x.is_cuda and x.dtype == torch.float16 and (R, S) in (
             (1, 1), (3, 3), (7, 7)) and (not reflect or stride == 1):
         # fp16 configs: cast through the bf16 MFMA path (see conv.py)

@@ -28,10 +28,11 @@ void mine_tgt_composite_bwd(const float*, const float*, const float*,
                             int, int, int, int, int, int, int, hipStream_t);
 void mine_conv_igemm_fwd(const void*, const void*, const float*, void*,
                          float*, int64_t, int, int, int, int, int, int, int,
-                         int, int, int, int, int, int, int, hipStream_t);
-void mine_conv_igemm_wrw(const void*, const void*, float*, int64_t, int, int,
+                         int, int, int, int, int, int, int, int, hipStream_t);
+int mine_conv_igemm_wrw_slabs(int64_t, int, int, int, int);
+void mine_conv_igemm_wrw(const void*, const void*, float*, float*, int64_t,
                          int, int, int, int, int, int, int, int, int, int,
-                         int, hipStream_t);
+                         int, int, int, hipStream_t);
 void mine_eav2_fwd(const float*, const float*, const float*, float*, int,
                    int, int, int64_t, int64_t, int64_t, int64_t,
                    hipStream_t);
@@ -65,10 +66,16 @@ void mine_mpi_head_bwd_f32(const void*, const float*, void*, int64_t, int,
                            hipStream_t);
 void mine_mpi_head_bwd_bf16(const void*, const float*, void*, int64_t, int,
                             hipStream_t);
-void mine_bn_stats_f32(const void*, float*, int64_t, int, int, hipStream_t);
-void mine_bn_stats_bf16(const void*, float*, int64_t, int, int, hipStream_t);
+void mine_bn_stats_f32(const void*, float*, int64_t, int, int, int,
+                       hipStream_t);
+void mine_bn_stats_bf16(const void*, float*, int64_t, int, int, int,
+                        hipStream_t);
+int mine_bn_reduce_grid_f32(int64_t, int, int);
+int mine_bn_reduce_grid_bf16(int64_t, int, int);
+void mine_bn_det_finish(const float*, int, int, float*, float*, float*,
+                        float*, float*, int64_t, float, float, hipStream_t);
 void mine_bn_join_stats_bf16(const void*, const void*, const void*, void*,
-                             float*, int64_t, int, int, int, int,
+                             float*, int64_t, int, int, int, int, int,
                              hipStream_t);
 void mine_bn_finalize(const float*, float*, float*, float*, float*, int64_t,
                       int, float, float, hipStream_t);
@@ -81,11 +88,11 @@ void mine_bn_act_fwd_bf16(const void*, const void*, const float*, const float*,
 void mine_bn_act_bwd_reduce_f32(const void*, const void*, const void*,
                                 const float*, const float*, const float*,
                                 const float*, float*, int64_t, int, int, int,
-                                hipStream_t);
+                                int, hipStream_t);
 void mine_bn_act_bwd_reduce_bf16(const void*, const void*, const void*,
                                  const float*, const float*, const float*,
                                  const float*, float*, int64_t, int, int, int,
-                                 hipStream_t);
+                                 int, hipStream_t);
 void mine_bn_act_bwd_dx_f32(const void*, const void*, const void*,
                             const float*, const float*, const float*,
                             const float*, const float*, void*, void*, int64_t,
@@ -253,7 +260,7 @@ at::Tensor conv_igemm_fwd(at::Tensor x_flat, at::Tensor wp, at::Tensor bias,
                           int64_t M, int64_t P, int64_t Q, int64_t K,
                           int64_t Hs, int64_t Ws, int64_t C, int64_t R,
                           int64_t S, int64_t SA, int64_t SB, int64_t SD,
-                          int64_t SE, int64_t pad_mode) {
+                          int64_t SE, int64_t pad_mode, bool deterministic) {
   TORCH_CHECK(x_flat.is_cuda() && x_flat.is_contiguous() &&
               wp.is_contiguous());
   TORCH_CHECK(x_flat.scalar_type() == at::kBFloat16 &&
@@ -271,7 +278,11 @@ at::Tensor conv_igemm_fwd(at::Tensor x_flat, at::Tensor wp, at::Tensor bias,
     if (splitz > nchunks / 4) splitz = (int)(nchunks / 4);
     if (splitz > 16) splitz = 16;
     if (splitz > 1) {
-      ws = at::zeros({M * K}, x_flat.options().dtype(at::kFloat));
+      // deterministic: one unfilled (M,K) slice per z, summed in ascending
+      // z by the epilogue; default: one zero-filled (M,K), atomics
+      const auto fopt = x_flat.options().dtype(at::kFloat);
+      ws = deterministic ? at::empty({splitz * M * K}, fopt)
+                         : at::zeros({M * K}, fopt);
       ws_ptr = ws.data_ptr<float>();
     }
   }
@@ -280,7 +291,7 @@ at::Tensor conv_igemm_fwd(at::Tensor x_flat, at::Tensor wp, at::Tensor bias,
                       out.data_ptr(), ws_ptr, M, (int)P, (int)Q, (int)K,
                       (int)Hs, (int)Ws, (int)C, (int)R, (int)S, (int)SA,
                       (int)SB, (int)SD, (int)SE, (int)pad_mode, splitz,
-                      stream());
+                      deterministic ? 1 : 0, stream());
   return out;
 }
 
@@ -288,14 +299,26 @@ at::Tensor conv_igemm_wrw(at::Tensor x_flat, at::Tensor gy_flat, int64_t M,
                           int64_t P, int64_t Q, int64_t K, int64_t Hs,
                           int64_t Ws, int64_t C, int64_t R, int64_t S,
                           int64_t SA, int64_t SB, int64_t SD, int64_t SE,
-                          int64_t pad_mode) {
+                          int64_t pad_mode, bool deterministic) {
   TORCH_CHECK(x_flat.is_cuda() && x_flat.is_contiguous() &&
               gy_flat.is_contiguous());
   TORCH_CHECK(x_flat.scalar_type() == at::kBFloat16 &&
               gy_flat.scalar_type() == at::kBFloat16);
-  auto dw = at::zeros({K, C, R, S}, x_flat.options().dtype(at::kFloat));
+  const auto fopt = x_flat.options().dtype(at::kFloat);
+  at::Tensor dw, ws;
+  float* ws_ptr = nullptr;
+  if (deterministic) {
+    // per-slab partials, summed in ascending slab order by the finish
+    const int slabs =
+        mine_conv_igemm_wrw_slabs(M, (int)K, (int)C, (int)R, (int)S);
+    ws = at::empty({slabs, K, C, R, S}, fopt);
+    ws_ptr = ws.data_ptr<float>();
+    dw = at::empty({K, C, R, S}, fopt);
+  } else {
+    dw = at::zeros({K, C, R, S}, fopt);
+  }
   mine_conv_igemm_wrw(x_flat.data_ptr(), gy_flat.data_ptr(),
-                      dw.data_ptr<float>(), M, (int)P, (int)Q, (int)K,
+                      dw.data_ptr<float>(), ws_ptr, M, (int)P, (int)Q, (int)K,
                       (int)Hs, (int)Ws, (int)C, (int)R, (int)S, (int)SA,
                       (int)SB, (int)SD, (int)SE, (int)pad_mode, stream());
   return dw;
@@ -524,11 +547,45 @@ at::Tensor mpi_head_bwd(at::Tensor z, at::Tensor gout, int64_t N, bool alpha) {
 // max_blocks (trailing, default 0 = automatic) caps grid.x of the BN
 // launches so a test can run the strided row loop and its tail at a
 // small shape.
-at::Tensor bn_sums(at::Tensor x, int64_t M, int64_t C, int64_t max_blocks) {
+//
+// deterministic (trailing, default false): the reduction kernels write
+// per-block partials into an unfilled [grid.x][2][C] workspace and
+// mine_bn_det_finish adds them in a fixed order (bn_kernels.hip).
+int bn_reduce_grid(at::ScalarType t, int64_t M, int64_t C,
+                   int64_t max_blocks) {
+  TORCH_CHECK(t == at::kFloat || t == at::kBFloat16,
+              "bn: dtype must be f32 or bf16");
+  return t == at::kFloat
+             ? mine_bn_reduce_grid_f32(M, (int)C, (int)max_blocks)
+             : mine_bn_reduce_grid_bf16(M, (int)C, (int)max_blocks);
+}
+
+// deterministic stats pass over x: returns the workspace and its grid.x
+at::Tensor bn_stats_partials(const at::Tensor& x, int64_t M, int64_t C,
+                             int64_t max_blocks, int* G) {
+  *G = bn_reduce_grid(x.scalar_type(), M, C, max_blocks);
+  auto ws = at::empty({*G, 2, C}, x.options().dtype(at::kFloat));
+  BN_DISPATCH(mine_bn_stats, x.scalar_type(), x.data_ptr(),
+              ws.data_ptr<float>(), M, (int)C, (int)max_blocks, 1, stream());
+  return ws;
+}
+
+at::Tensor bn_sums(at::Tensor x, int64_t M, int64_t C, int64_t max_blocks,
+                   bool deterministic) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.numel() == M * C);
+  if (deterministic) {
+    int G = 0;
+    auto ws = bn_stats_partials(x, M, C, max_blocks, &G);
+    auto sums = at::empty({2 * C}, ws.options());
+    mine_bn_det_finish(ws.data_ptr<float>(), G, (int)C,
+                       sums.data_ptr<float>(), nullptr, nullptr, nullptr,
+                       nullptr, M, 0.0f, 0.0f, stream());
+    return sums;
+  }
   auto sums = at::zeros({2 * C}, x.options().dtype(at::kFloat));
   BN_DISPATCH(mine_bn_stats, x.scalar_type(), x.data_ptr(),
-              sums.data_ptr<float>(), M, (int)C, (int)max_blocks, stream());
+              sums.data_ptr<float>(), M, (int)C, (int)max_blocks, 0,
+              stream());
   return sums;
 }
 
@@ -553,8 +610,24 @@ std::vector<at::Tensor> bn_finalize(at::Tensor sums, int64_t M, int64_t C,
 std::vector<at::Tensor> bn_stats(at::Tensor x, int64_t M, int64_t C,
                                  at::Tensor running_mean,
                                  at::Tensor running_var, double eps,
-                                 double momentum, int64_t max_blocks) {
-  return bn_finalize(bn_sums(x, M, C, max_blocks), M, C, running_mean,
+                                 double momentum, int64_t max_blocks,
+                                 bool deterministic) {
+  if (deterministic) {
+    // the finishing kernel also finalizes: two launches, no zero fill
+    TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.numel() == M * C);
+    int G = 0;
+    auto ws = bn_stats_partials(x, M, C, max_blocks, &G);
+    auto mean = at::empty({C}, ws.options());
+    auto invstd = at::empty({C}, ws.options());
+    const bool track = running_mean.numel() > 0;
+    mine_bn_det_finish(ws.data_ptr<float>(), G, (int)C, nullptr,
+                       mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                       track ? running_mean.data_ptr<float>() : nullptr,
+                       track ? running_var.data_ptr<float>() : nullptr, M,
+                       (float)eps, (float)momentum, stream());
+    return {mean, invstd};
+  }
+  return bn_finalize(bn_sums(x, M, C, max_blocks, false), M, C, running_mean,
                      running_var, eps, momentum);
 }
 
@@ -564,7 +637,8 @@ std::vector<at::Tensor> bn_stats(at::Tensor x, int64_t M, int64_t C,
 std::vector<at::Tensor> bn_join_stats(at::Tensor y_dec, at::Tensor y_base,
                                       at::Tensor bias, int64_t B, int64_t S,
                                       int64_t HW, int64_t C,
-                                      int64_t max_blocks) {
+                                      int64_t max_blocks,
+                                      bool deterministic) {
   TORCH_CHECK(y_dec.is_cuda() && y_dec.is_contiguous() &&
               y_base.is_contiguous() && bias.is_contiguous());
   TORCH_CHECK(y_dec.scalar_type() == at::kBFloat16 &&
@@ -576,11 +650,27 @@ std::vector<at::Tensor> bn_join_stats(at::Tensor y_dec, at::Tensor y_base,
   TORCH_CHECK(y_dec.numel() == B * S * HW * C &&
               y_base.numel() == B * HW * C && bias.numel() == B * S * C);
   auto x = at::empty_like(y_dec);
-  auto sums = at::zeros({2 * C}, y_dec.options().dtype(at::kFloat));
+  const auto fopt = y_dec.options().dtype(at::kFloat);
+  if (deterministic) {
+    // the finish launch takes the place of the zero fill
+    const int64_t M = B * S * HW;
+    const int G = bn_reduce_grid(at::kBFloat16, M, C, max_blocks);
+    auto ws = at::empty({G, 2, C}, fopt);
+    auto sums = at::empty({2 * C}, fopt);
+    mine_bn_join_stats_bf16(y_dec.data_ptr(), y_base.data_ptr(),
+                            bias.data_ptr(), x.data_ptr(),
+                            ws.data_ptr<float>(), M, (int)HW, (int)S, (int)C,
+                            (int)max_blocks, 1, stream());
+    mine_bn_det_finish(ws.data_ptr<float>(), G, (int)C,
+                       sums.data_ptr<float>(), nullptr, nullptr, nullptr,
+                       nullptr, M, 0.0f, 0.0f, stream());
+    return {x, sums};
+  }
+  auto sums = at::zeros({2 * C}, fopt);
   mine_bn_join_stats_bf16(y_dec.data_ptr(), y_base.data_ptr(),
                           bias.data_ptr(), x.data_ptr(),
                           sums.data_ptr<float>(), B * S * HW, (int)HW, (int)S,
-                          (int)C, (int)max_blocks, stream());
+                          (int)C, (int)max_blocks, 0, stream());
   return {x, sums};
 }
 
@@ -602,17 +692,32 @@ at::Tensor bn_act_fwd(at::Tensor x, at::Tensor res, at::Tensor mean,
 at::Tensor bn_act_bwd_reduce(at::Tensor x, at::Tensor res, at::Tensor gy,
                              at::Tensor mean, at::Tensor invstd,
                              at::Tensor gamma, at::Tensor beta, int64_t M,
-                             int64_t C, int64_t act, int64_t max_blocks) {
+                             int64_t C, int64_t act, int64_t max_blocks,
+                             bool deterministic) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && gy.is_contiguous());
   TORCH_CHECK(act >= 0 && act <= 4, "bn: unknown activation");
-  auto red = at::zeros({2 * C}, x.options().dtype(at::kFloat));
+  const auto fopt = x.options().dtype(at::kFloat);
   const bool add_relu = act == 4;
+  at::Tensor red, ws;
+  int G = 0;
+  if (deterministic) {
+    G = bn_reduce_grid(x.scalar_type(), M, C, max_blocks);
+    ws = at::empty({G, 2, C}, fopt);
+    red = at::empty({2 * C}, fopt);
+  } else {
+    red = at::zeros({2 * C}, fopt);
+  }
   BN_DISPATCH(mine_bn_act_bwd_reduce, x.scalar_type(), x.data_ptr(),
               add_relu ? res.data_ptr() : nullptr, gy.data_ptr(),
               mean.data_ptr<float>(), invstd.data_ptr<float>(),
               gamma.data_ptr<float>(), beta.data_ptr<float>(),
-              red.data_ptr<float>(), M, (int)C, (int)act, (int)max_blocks,
+              deterministic ? ws.data_ptr<float>() : red.data_ptr<float>(), M,
+              (int)C, (int)act, (int)max_blocks, deterministic ? 1 : 0,
               stream());
+  if (deterministic)
+    mine_bn_det_finish(ws.data_ptr<float>(), G, (int)C, red.data_ptr<float>(),
+                       nullptr, nullptr, nullptr, nullptr, M, 0.0f, 0.0f,
+                       stream());
   return red;  // (dbeta, dgamma)
 }
 
@@ -650,9 +755,9 @@ std::vector<at::Tensor> bn_act_bwd(at::Tensor x, at::Tensor res,
                                    at::Tensor gy, at::Tensor mean,
                                    at::Tensor invstd, at::Tensor gamma,
                                    at::Tensor beta, int64_t M, int64_t C,
-                                   int64_t act) {
+                                   int64_t act, bool deterministic) {
   auto red = bn_act_bwd_reduce(x, res, gy, mean, invstd, gamma, beta,
-                               M, C, act, 0);
+                               M, C, act, 0, deterministic);
   auto dxr = bn_act_bwd_dx(x, res, gy, mean, invstd, gamma, beta, red,
                            M, C, act, M, 0);
   // dgamma = red[C:], dbeta = red[:C]; nothing writes `red` after the
@@ -723,10 +828,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("eav2_bwd", &eav2_bwd, "fused edge-aware smoothness v2 bwd");
   mod.def("pack_gather", &pack_gather,
           "one-launch fragment pack through a device LUT");
+  namespace py = pybind11;
   mod.def("conv_igemm_fwd", &conv_igemm_fwd,
-          "general igemm conv fwd / data-grad (coordinate-remapped)");
+          "general igemm conv fwd / data-grad (coordinate-remapped)",
+          py::arg("x_flat"), py::arg("wp"), py::arg("bias"), py::arg("M"),
+          py::arg("P"), py::arg("Q"), py::arg("K"), py::arg("Hs"),
+          py::arg("Ws"), py::arg("C"), py::arg("R"), py::arg("S"),
+          py::arg("SA"), py::arg("SB"), py::arg("SD"), py::arg("SE"),
+          py::arg("pad_mode"), py::arg("deterministic") = false);
   mod.def("conv_igemm_wrw", &conv_igemm_wrw,
-          "general igemm conv weight-grad");
+          "general igemm conv weight-grad", py::arg("x_flat"),
+          py::arg("gy_flat"), py::arg("M"), py::arg("P"), py::arg("Q"),
+          py::arg("K"), py::arg("Hs"), py::arg("Ws"), py::arg("C"),
+          py::arg("R"), py::arg("S"), py::arg("SA"), py::arg("SB"),
+          py::arg("SD"), py::arg("SE"), py::arg("pad_mode"),
+          py::arg("deterministic") = false);
   mod.def("upsample2x_fwd", &upsample2x_fwd,
           "nearest x2 upsample fwd, flat NHWC");
   mod.def("upsample2x_bwd", &upsample2x_bwd,
@@ -735,33 +851,36 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "gather reflection pad over logical (N,H,W,C)");
   mod.def("reflect_pad_bwd", &reflect_pad_bwd,
           "gather (atomic-free) reflection pad backward");
-  namespace py = pybind11;
   mod.def("bn_stats", &bn_stats,
           "per-channel mean/invstd + running-stat update", py::arg("x"),
           py::arg("M"), py::arg("C"), py::arg("running_mean"),
           py::arg("running_var"), py::arg("eps"), py::arg("momentum"),
-          py::arg("max_blocks") = 0);
+          py::arg("max_blocks") = 0, py::arg("deterministic") = false);
   mod.def("bn_sums", &bn_sums,
           "per-channel (sum, sumsq) only — for cross-rank SyncBN",
           py::arg("x"), py::arg("M"), py::arg("C"),
-          py::arg("max_blocks") = 0);
+          py::arg("max_blocks") = 0, py::arg("deterministic") = false);
   mod.def("bn_finalize", &bn_finalize,
           "(sum, sumsq) -> mean/invstd + running-stat update");
   mod.def("bn_join_stats", &bn_join_stats,
           "x = (y_base + bias) + y_dec with its per-channel (sum, sumsq)",
           py::arg("y_dec"), py::arg("y_base"), py::arg("bias"), py::arg("B"),
           py::arg("S"), py::arg("HW"), py::arg("C"),
-          py::arg("max_blocks") = 0);
+          py::arg("max_blocks") = 0, py::arg("deterministic") = false);
   mod.def("bn_act_fwd", &bn_act_fwd, "fused normalize + activation",
           py::arg("x"), py::arg("res"), py::arg("mean"), py::arg("invstd"),
           py::arg("gamma"), py::arg("beta"), py::arg("M"), py::arg("C"),
           py::arg("act"), py::arg("max_blocks") = 0);
   mod.def("bn_act_bwd", &bn_act_bwd,
-          "fused BN+act backward -> dx, dres, dgamma, dbeta");
+          "fused BN+act backward -> dx, dres, dgamma, dbeta", py::arg("x"),
+          py::arg("res"), py::arg("gy"), py::arg("mean"), py::arg("invstd"),
+          py::arg("gamma"), py::arg("beta"), py::arg("M"), py::arg("C"),
+          py::arg("act"), py::arg("deterministic") = false);
   mod.def("bn_act_bwd_reduce", &bn_act_bwd_reduce, py::arg("x"),
           py::arg("res"), py::arg("gy"), py::arg("mean"), py::arg("invstd"),
           py::arg("gamma"), py::arg("beta"), py::arg("M"), py::arg("C"),
-          py::arg("act"), py::arg("max_blocks") = 0);
+          py::arg("act"), py::arg("max_blocks") = 0,
+          py::arg("deterministic") = false);
   mod.def("bn_act_bwd_dx", &bn_act_bwd_dx, py::arg("x"), py::arg("res"),
           py::arg("gy"), py::arg("mean"), py::arg("invstd"), py::arg("gamma"),
           py::arg("beta"), py::arg("red"), py::arg("M"), py::arg("C"),

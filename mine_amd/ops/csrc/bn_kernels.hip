@@ -16,6 +16,15 @@
 // channels_last), reduce through LDS, then one fp32 atomicAdd per block
 // into the output accumulator. ~1e-8-relative partial-sum error at the
 // flagship sizes; backward is the same shape.
+//
+// Deterministic mode (DET = true instantiations of the five reduction
+// kernels): same lane map and grid, so every thread sums the same rows,
+// but no atomics. Each thread stores its partials to LDS at
+// [row-in-block][channel]; after the barrier one thread per channel adds
+// the kBlock/cg rows in ascending order and stores the block's (2, nc)
+// result with plain stores into a workspace [gridDim.x][2][C].
+// bn_det_finish_kernel then adds the gridDim.x partials per channel in a
+// fixed order (see its comment) and optionally finalizes.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -90,19 +99,42 @@ inline __host__ __device__ int chan_group(int C) {
   return g;
 }
 
-template <typename T>
+// Deterministic block combine. The caller has stored its V partials at
+// s_a/s_b[threadIdx.x * V + j], which IS [row][channel] with rows of
+// `width` = cg*V floats (tid = row*cg + lane_c). Column i of row r sits
+// at r*width + i, so consecutive threads read consecutive banks. Rows are
+// added in ascending order; the result goes to ws[blockIdx.x][2][C] at
+// channel col0 + i.
+__device__ __forceinline__ void det_block_flush(
+    const float* __restrict__ s_a, const float* __restrict__ s_b, int width,
+    int rows, int ncols, float* __restrict__ ws, int C, int col0) {
+  float* wa = ws + (int64_t)blockIdx.x * 2 * C + col0;
+  for (int i = threadIdx.x; i < ncols; i += kBlock) {
+    float ta = 0.0f, tb = 0.0f;
+    for (int r = 0; r < rows; ++r) {
+      ta += s_a[r * width + i];
+      tb += s_b[r * width + i];
+    }
+    wa[i] = ta;
+    wa[C + i] = tb;
+  }
+}
+
+template <typename T, bool DET>
 __global__ void __launch_bounds__(kBlock)
 bn_stats_kernel(const T* __restrict__ x, float* __restrict__ sums,  // (2,C)
                 int64_t M, int C, int cg) {
   // grid.x: slabs of the M axis; grid.y: channel chunks of cg
   const int c0 = blockIdx.y * cg;
   const int nc = min(cg, C - c0);
-  __shared__ float s_sum[64], s_sq[64];
-  for (int i = threadIdx.x; i < cg; i += kBlock) {
-    s_sum[i] = 0.0f;
-    s_sq[i] = 0.0f;
+  __shared__ float s_sum[DET ? kBlock : 64], s_sq[DET ? kBlock : 64];
+  if constexpr (!DET) {
+    for (int i = threadIdx.x; i < cg; i += kBlock) {
+      s_sum[i] = 0.0f;
+      s_sq[i] = 0.0f;
+    }
+    __syncthreads();
   }
-  __syncthreads();
 
   const int lane_c = threadIdx.x & (cg - 1);
   const int rows_per_blk = kBlock / cg;
@@ -116,10 +148,19 @@ bn_stats_kernel(const T* __restrict__ x, float* __restrict__ sums,  // (2,C)
       lsum += v;
       lsq += v * v;
     }
-    atomicAdd(&s_sum[lane_c], lsum);
-    atomicAdd(&s_sq[lane_c], lsq);
+    if constexpr (DET) {
+      s_sum[threadIdx.x] = lsum;
+      s_sq[threadIdx.x] = lsq;
+    } else {
+      atomicAdd(&s_sum[lane_c], lsum);
+      atomicAdd(&s_sq[lane_c], lsq);
+    }
   }
   __syncthreads();
+  if constexpr (DET) {
+    det_block_flush(s_sum, s_sq, cg, rows_per_blk, nc, sums, C, c0);
+    return;
+  }
   for (int i = threadIdx.x; i < nc; i += kBlock) {
     atomicAdd(&sums[c0 + i], s_sum[i]);
     atomicAdd(&sums[C + c0 + i], s_sq[i]);
@@ -145,6 +186,83 @@ __global__ void bn_finalize_kernel(const float* __restrict__ sums,
     running_mean[c] += momentum * (mu - running_mean[c]);
     const float unbiased = M > 1 ? var * (float)M / (float)(M - 1) : var;
     running_var[c] += momentum * (unbiased - running_var[c]);
+  }
+}
+
+// Deterministic finish: adds the G per-block partials ws[g][2][C] of each
+// channel in a FIXED TWO-LEVEL ORDER that depends only on (G, C):
+//   level 1: with cw = min(chan_group(C), 16) channels per block and
+//            np = kBlock/cw >= 16 partial lanes, lane p adds blocks
+//            g = p, p+np, p+2np, ... in ascending g (cw is capped so the
+//            2048-partial chains of the wide layers stay <= 128 long;
+//            four loads are issued ahead of their adds, the adds stay in
+//            order);
+//   level 2: one thread per channel adds the np lane partials in
+//            ascending p.
+// Then it writes the (2, C) sums to `out` (bn_sums, bn_join_stats,
+// bn_act_bwd_reduce) and/or, when `mean` is given, finalizes exactly as
+// bn_finalize_kernel does (bn_stats) — so the mode adds no launch. A
+// separate launch after the reduction: no device-wide fence, no
+// last-block-to-arrive.
+__global__ void __launch_bounds__(kBlock)
+bn_det_finish_kernel(const float* __restrict__ ws, int G, int C, int cw,
+                     float* __restrict__ out, float* __restrict__ mean,
+                     float* __restrict__ invstd,
+                     float* __restrict__ running_mean,
+                     float* __restrict__ running_var, int64_t M, float eps,
+                     float momentum) {
+  __shared__ float s_a[kBlock], s_b[kBlock];
+  const int lane_c = threadIdx.x & (cw - 1);
+  const int p = threadIdx.x / cw;
+  const int np = kBlock / cw;
+  const int c = blockIdx.x * cw + lane_c;
+  float a = 0.0f, b = 0.0f;
+  if (c < C) {
+    const int64_t step = (int64_t)np * 2 * C;
+    const float* row = ws + (int64_t)p * 2 * C + c;
+    int g = p;
+    for (; g + 3 * np < G; g += 4 * np, row += 4 * step) {
+      float va[4], vb[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        va[u] = row[u * step];
+        vb[u] = row[u * step + C];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        a += va[u];
+        b += vb[u];
+      }
+    }
+    for (; g < G; g += np, row += step) {
+      a += row[0];
+      b += row[C];
+    }
+  }
+  s_a[threadIdx.x] = a;  // [p][lane_c]
+  s_b[threadIdx.x] = b;
+  __syncthreads();
+  if (threadIdx.x >= cw || c >= C) return;
+  float ta = 0.0f, tb = 0.0f;
+  for (int q = 0; q < np; ++q) {
+    ta += s_a[q * cw + lane_c];
+    tb += s_b[q * cw + lane_c];
+  }
+  if (out) {
+    out[c] = ta;
+    out[C + c] = tb;
+  }
+  if (mean) {
+    const float mu = ta / (float)M;
+    float var = tb / (float)M - mu * mu;
+    var = var > 0.0f ? var : 0.0f;
+    mean[c] = mu;
+    invstd[c] = rsqrtf(var + eps);
+    if (running_mean) {
+      running_mean[c] += momentum * (mu - running_mean[c]);
+      const float unbiased = M > 1 ? var * (float)M / (float)(M - 1) : var;
+      running_var[c] += momentum * (unbiased - running_var[c]);
+    }
   }
 }
 
@@ -179,7 +297,7 @@ bn_act_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res,
 //   where g' = gy * act'(z), z recomputed from x
 // ---------------------------------------------------------------------------
 
-template <typename T>
+template <typename T, bool DET>
 __global__ void __launch_bounds__(kBlock)
 bn_act_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ res,
                          const T* __restrict__ gy,
@@ -191,12 +309,14 @@ bn_act_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ res,
                          int64_t M, int C, int act, int cg) {
   const int c0 = blockIdx.y * cg;
   const int nc = min(cg, C - c0);
-  __shared__ float s_db[64], s_dg[64];
-  for (int i = threadIdx.x; i < cg; i += kBlock) {
-    s_db[i] = 0.0f;
-    s_dg[i] = 0.0f;
+  __shared__ float s_db[DET ? kBlock : 64], s_dg[DET ? kBlock : 64];
+  if constexpr (!DET) {
+    for (int i = threadIdx.x; i < cg; i += kBlock) {
+      s_db[i] = 0.0f;
+      s_dg[i] = 0.0f;
+    }
+    __syncthreads();
   }
-  __syncthreads();
   const int lane_c = threadIdx.x & (cg - 1);
   const int rows_per_blk = kBlock / cg;
   const int row0 = blockIdx.x * rows_per_blk + threadIdx.x / cg;
@@ -213,10 +333,19 @@ bn_act_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ res,
       db += g;
       dg += g * xh;
     }
-    atomicAdd(&s_db[lane_c], db);
-    atomicAdd(&s_dg[lane_c], dg);
+    if constexpr (DET) {
+      s_db[threadIdx.x] = db;
+      s_dg[threadIdx.x] = dg;
+    } else {
+      atomicAdd(&s_db[lane_c], db);
+      atomicAdd(&s_dg[lane_c], dg);
+    }
   }
   __syncthreads();
+  if constexpr (DET) {
+    det_block_flush(s_db, s_dg, cg, rows_per_blk, nc, out, C, c0);
+    return;
+  }
   for (int i = threadIdx.x; i < nc; i += kBlock) {
     atomicAdd(&out[c0 + i], s_db[i]);
     atomicAdd(&out[C + c0 + i], s_dg[i]);
@@ -276,7 +405,7 @@ inline __host__ __device__ int chan_group_v(int Cv) {
   return g;
 }
 
-template <typename T, int V>
+template <typename T, int V, bool DET>
 __global__ void __launch_bounds__(kBlock)
 bn_stats_vec_kernel(const T* __restrict__ x, float* __restrict__ sums,
                     int64_t M, int C, int cgv) {
@@ -284,12 +413,14 @@ bn_stats_vec_kernel(const T* __restrict__ x, float* __restrict__ sums,
   const int Cv = C / V;
   const int c0v = blockIdx.y * cgv;
   const int ncv = min(cgv, Cv - c0v);
-  __shared__ float s_sum[512], s_sq[512];
-  for (int i = threadIdx.x; i < cgv * V; i += kBlock) {
-    s_sum[i] = 0.0f;
-    s_sq[i] = 0.0f;
+  __shared__ float s_sum[DET ? kBlock * V : 512], s_sq[DET ? kBlock * V : 512];
+  if constexpr (!DET) {
+    for (int i = threadIdx.x; i < cgv * V; i += kBlock) {
+      s_sum[i] = 0.0f;
+      s_sq[i] = 0.0f;
+    }
+    __syncthreads();
   }
-  __syncthreads();
 
   const int lane_cv = threadIdx.x & (cgv - 1);
   const int rows_per_blk = kBlock / cgv;
@@ -311,11 +442,21 @@ bn_stats_vec_kernel(const T* __restrict__ x, float* __restrict__ sums,
     }
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      atomicAdd(&s_sum[lane_cv * V + j], acc[j]);
-      atomicAdd(&s_sq[lane_cv * V + j], asq[j]);
+      if constexpr (DET) {
+        s_sum[threadIdx.x * V + j] = acc[j];
+        s_sq[threadIdx.x * V + j] = asq[j];
+      } else {
+        atomicAdd(&s_sum[lane_cv * V + j], acc[j]);
+        atomicAdd(&s_sq[lane_cv * V + j], asq[j]);
+      }
     }
   }
   __syncthreads();
+  if constexpr (DET) {
+    det_block_flush(s_sum, s_sq, cgv * V, rows_per_blk, ncv * V, sums, C,
+                    c0v * V);
+    return;
+  }
   for (int i = threadIdx.x; i < ncv * V; i += kBlock) {
     atomicAdd(&sums[c0v * V + i], s_sum[i]);
     atomicAdd(&sums[C + c0v * V + i], s_sq[i]);
@@ -342,7 +483,7 @@ bn_stats_vec_kernel(const T* __restrict__ x, float* __restrict__ sums,
 constexpr int fwd_unroll(int act) { return act == ACT_ADD_RELU ? 1 : 3; }
 constexpr int dx_unroll(int act) { return act == ACT_ADD_RELU ? 1 : 2; }
 
-template <typename T, int V, int ACT>
+template <typename T, int V, int ACT, bool DET>
 __global__ void __launch_bounds__(kBlock)
 bn_act_bwd_reduce_vec_kernel(const T* __restrict__ x,
                              const T* __restrict__ res,
@@ -357,12 +498,14 @@ bn_act_bwd_reduce_vec_kernel(const T* __restrict__ x,
   const int Cv = C / V;
   const int c0v = blockIdx.y * cgv;
   const int ncv = min(cgv, Cv - c0v);
-  __shared__ float s_db[512], s_dg[512];
-  for (int i = threadIdx.x; i < cgv * V; i += kBlock) {
-    s_db[i] = 0.0f;
-    s_dg[i] = 0.0f;
+  __shared__ float s_db[DET ? kBlock * V : 512], s_dg[DET ? kBlock * V : 512];
+  if constexpr (!DET) {
+    for (int i = threadIdx.x; i < cgv * V; i += kBlock) {
+      s_db[i] = 0.0f;
+      s_dg[i] = 0.0f;
+    }
+    __syncthreads();
   }
-  __syncthreads();
   const int lane_cv = threadIdx.x & (cgv - 1);
   const int rows_per_blk = kBlock / cgv;
   const int row0 = blockIdx.x * rows_per_blk + threadIdx.x / cgv;
@@ -399,11 +542,21 @@ bn_act_bwd_reduce_vec_kernel(const T* __restrict__ x,
     }
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      atomicAdd(&s_db[lane_cv * V + j], db[j]);
-      atomicAdd(&s_dg[lane_cv * V + j], dg[j]);
+      if constexpr (DET) {
+        s_db[threadIdx.x * V + j] = db[j];
+        s_dg[threadIdx.x * V + j] = dg[j];
+      } else {
+        atomicAdd(&s_db[lane_cv * V + j], db[j]);
+        atomicAdd(&s_dg[lane_cv * V + j], dg[j]);
+      }
     }
   }
   __syncthreads();
+  if constexpr (DET) {
+    det_block_flush(s_db, s_dg, cgv * V, rows_per_blk, ncv * V, out, C,
+                    c0v * V);
+    return;
+  }
   for (int i = threadIdx.x; i < ncv * V; i += kBlock) {
     atomicAdd(&out[c0v * V + i], s_db[i]);
     atomicAdd(&out[C + c0v * V + i], s_dg[i]);
@@ -578,7 +731,7 @@ bn_act_bwd_dx_vec_kernel(const T* __restrict__ x, const T* __restrict__ res,
 // row stride, so the loop has no division.
 // ---------------------------------------------------------------------------
 
-template <int V>
+template <int V, bool DET>
 __global__ void __launch_bounds__(kBlock)
 bn_join_stats_vec_kernel(const __hip_bfloat16* __restrict__ y_dec,
                          const __hip_bfloat16* __restrict__ y_base,
@@ -591,12 +744,14 @@ bn_join_stats_vec_kernel(const __hip_bfloat16* __restrict__ y_dec,
   const int Cv = C / V;
   const int c0v = blockIdx.y * cgv;
   const int ncv = min(cgv, Cv - c0v);
-  __shared__ float s_sum[512], s_sq[512];
-  for (int i = threadIdx.x; i < cgv * V; i += kBlock) {
-    s_sum[i] = 0.0f;
-    s_sq[i] = 0.0f;
+  __shared__ float s_sum[DET ? kBlock * V : 512], s_sq[DET ? kBlock * V : 512];
+  if constexpr (!DET) {
+    for (int i = threadIdx.x; i < cgv * V; i += kBlock) {
+      s_sum[i] = 0.0f;
+      s_sq[i] = 0.0f;
+    }
+    __syncthreads();
   }
-  __syncthreads();
 
   const int lane_cv = threadIdx.x & (cgv - 1);
   const int rows_per_blk = kBlock / cgv;
@@ -646,11 +801,21 @@ bn_join_stats_vec_kernel(const __hip_bfloat16* __restrict__ y_dec,
     }
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-      atomicAdd(&s_sum[lane_cv * V + j], acc[j]);
-      atomicAdd(&s_sq[lane_cv * V + j], asq[j]);
+      if constexpr (DET) {
+        s_sum[threadIdx.x * V + j] = acc[j];
+        s_sq[threadIdx.x * V + j] = asq[j];
+      } else {
+        atomicAdd(&s_sum[lane_cv * V + j], acc[j]);
+        atomicAdd(&s_sq[lane_cv * V + j], asq[j]);
+      }
     }
   }
   __syncthreads();
+  if constexpr (DET) {
+    det_block_flush(s_sum, s_sq, cgv * V, rows_per_blk, ncv * V, sums, C,
+                    c0v * V);
+    return;
+  }
   for (int i = threadIdx.x; i < ncv * V; i += kBlock) {
     atomicAdd(&sums[c0v * V + i], s_sum[i]);
     atomicAdd(&sums[C + c0v * V + i], s_sq[i]);
@@ -711,7 +876,20 @@ inline dim3 grid_elems_capped(int64_t total, int max_blocks) {
     default: LAUNCH(ACT_NONE); break;              \
   }
 
+// grid.x of the reduction kernels for (M, C): the deterministic mode's
+// workspace has that many (2, C) partials.
 template <typename T>
+int reduce_grid_x(int64_t M, int C, int max_blocks) {
+  constexpr int V = 16 / (int)sizeof(T);
+  if (C % V == 0) {
+    const int Cv = C / V;
+    return (int)grid_reduce_v(M, Cv, chan_group_v(Cv), max_blocks).x;
+  }
+  return (int)grid_reduce(M, C, chan_group(C), max_blocks).x;
+}
+
+// DET: `sums` is the [grid.x][2][C] workspace (no zero fill needed)
+template <typename T, bool DET>
 void launch_bn_stats(const void* x, float* sums, int64_t M, int C,
                      int max_blocks, hipStream_t s) {
   constexpr int V = 16 / (int)sizeof(T);
@@ -719,14 +897,15 @@ void launch_bn_stats(const void* x, float* sums, int64_t M, int C,
   if (C % V == 0) {
     const int Cv = C / V;
     const int cgv = chan_group_v(Cv);
-    hipLaunchKernelGGL((bn_stats_vec_kernel<T, V>),
+    hipLaunchKernelGGL((bn_stats_vec_kernel<T, V, DET>),
                        grid_reduce_v(M, Cv, cgv, max_blocks), dim3(kBlock), 0,
                        s, xp, sums, M, C, cgv);
     return;
   }
   const int cg = chan_group(C);
-  hipLaunchKernelGGL(bn_stats_kernel<T>, grid_reduce(M, C, cg, max_blocks),
-                     dim3(kBlock), 0, s, xp, sums, M, C, cg);
+  hipLaunchKernelGGL((bn_stats_kernel<T, DET>),
+                     grid_reduce(M, C, cg, max_blocks), dim3(kBlock), 0, s, xp,
+                     sums, M, C, cg);
 }
 
 template <typename T>
@@ -755,7 +934,8 @@ void launch_bn_act_fwd(const void* x, const void* res, const float* mean,
                      xp, rp, mean, invstd, gamma, beta, yp, M, C, act);
 }
 
-template <typename T>
+// DET: `out` is the [grid.x][2][C] workspace
+template <typename T, bool DET>
 void launch_bn_act_bwd_reduce(const void* x, const void* res, const void* gy,
                               const float* mean, const float* invstd,
                               const float* gamma, const float* beta,
@@ -770,7 +950,7 @@ void launch_bn_act_bwd_reduce(const void* x, const void* res, const void* gy,
     const int cgv = chan_group_v(Cv);
     const dim3 grid = grid_reduce_v(M, Cv, cgv, max_blocks);
 #define BN_LAUNCH(A)                                                        \
-  hipLaunchKernelGGL((bn_act_bwd_reduce_vec_kernel<T, V, A>), grid,         \
+  hipLaunchKernelGGL((bn_act_bwd_reduce_vec_kernel<T, V, A, DET>), grid,    \
                      dim3(kBlock), 0, s, xp, rp, gp, mean, invstd, gamma,   \
                      beta, out, M, C, cgv)
     BN_ACT_SWITCH(act, BN_LAUNCH)
@@ -778,7 +958,7 @@ void launch_bn_act_bwd_reduce(const void* x, const void* res, const void* gy,
     return;
   }
   const int cg = chan_group(C);
-  hipLaunchKernelGGL(bn_act_bwd_reduce_kernel<T>,
+  hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<T, DET>),
                      grid_reduce(M, C, cg, max_blocks), dim3(kBlock), 0, s, xp,
                      rp, gp, mean, invstd, gamma, beta, out, M, C, act, cg);
 }
@@ -817,8 +997,13 @@ void launch_bn_act_bwd_dx(const void* x, const void* res, const void* gy,
 
 #define EXPORT_BN(SUF, T)                                                      \
   extern "C" void mine_bn_stats_##SUF(const void* x, float* sums, int64_t M,   \
-                                      int C, int max_blocks, hipStream_t s) {  \
-    launch_bn_stats<T>(x, sums, M, C, max_blocks, s);                          \
+                                      int C, int max_blocks, int det,          \
+                                      hipStream_t s) {                         \
+    if (det) launch_bn_stats<T, true>(x, sums, M, C, max_blocks, s);           \
+    else launch_bn_stats<T, false>(x, sums, M, C, max_blocks, s);              \
+  }                                                                            \
+  extern "C" int mine_bn_reduce_grid_##SUF(int64_t M, int C, int max_blocks) { \
+    return reduce_grid_x<T>(M, C, max_blocks);                                 \
   }                                                                            \
   extern "C" void mine_bn_act_fwd_##SUF(                                       \
       const void* x, const void* res, const float* mean, const float* invstd,  \
@@ -830,9 +1015,13 @@ void launch_bn_act_bwd_dx(const void* x, const void* res, const void* gy,
   extern "C" void mine_bn_act_bwd_reduce_##SUF(                                \
       const void* x, const void* res, const void* gy, const float* mean,       \
       const float* invstd, const float* gamma, const float* beta, float* out,  \
-      int64_t M, int C, int act, int max_blocks, hipStream_t s) {              \
-    launch_bn_act_bwd_reduce<T>(x, res, gy, mean, invstd, gamma, beta, out, M, \
-                                C, act, max_blocks, s);                        \
+      int64_t M, int C, int act, int max_blocks, int det, hipStream_t s) {     \
+    if (det)                                                                   \
+      launch_bn_act_bwd_reduce<T, true>(x, res, gy, mean, invstd, gamma, beta, \
+                                        out, M, C, act, max_blocks, s);        \
+    else                                                                       \
+      launch_bn_act_bwd_reduce<T, false>(x, res, gy, mean, invstd, gamma,      \
+                                         beta, out, M, C, act, max_blocks, s); \
   }                                                                            \
   extern "C" void mine_bn_act_bwd_dx_##SUF(                                    \
       const void* x, const void* res, const void* gy, const float* mean,       \
@@ -850,17 +1039,36 @@ EXPORT_BN(bf16, __hip_bfloat16)
 extern "C" void mine_bn_join_stats_bf16(const void* y_dec, const void* y_base,
                                         const void* bias, void* x, float* sums,
                                         int64_t M, int HW, int S, int C,
-                                        int max_blocks, hipStream_t s) {
+                                        int max_blocks, int det,
+                                        hipStream_t s) {
   constexpr int V = 8;
   const int Cv = C / V;
   const int cgv = chan_group_v(Cv);
-  hipLaunchKernelGGL(bn_join_stats_vec_kernel<V>,
-                     grid_reduce_v(M, Cv, cgv, max_blocks), dim3(kBlock), 0, s,
-                     reinterpret_cast<const __hip_bfloat16*>(y_dec),
-                     reinterpret_cast<const __hip_bfloat16*>(y_base),
-                     reinterpret_cast<const __hip_bfloat16*>(bias),
-                     reinterpret_cast<__hip_bfloat16*>(x), sums, M, HW, S, C,
-                     cgv);
+#define JOIN_LAUNCH(DET)                                                      \
+  hipLaunchKernelGGL((bn_join_stats_vec_kernel<V, DET>),                      \
+                     grid_reduce_v(M, Cv, cgv, max_blocks), dim3(kBlock), 0,  \
+                     s, reinterpret_cast<const __hip_bfloat16*>(y_dec),       \
+                     reinterpret_cast<const __hip_bfloat16*>(y_base),         \
+                     reinterpret_cast<const __hip_bfloat16*>(bias),           \
+                     reinterpret_cast<__hip_bfloat16*>(x), sums, M, HW, S, C, \
+                     cgv)
+  if (det) JOIN_LAUNCH(true);
+  else JOIN_LAUNCH(false);
+#undef JOIN_LAUNCH
+}
+
+// deterministic finish over ws[G][2][C]: writes `out` (2,C) if given and
+// finalizes into mean/invstd (+ running stats) if given
+extern "C" void mine_bn_det_finish(const float* ws, int G, int C, float* out,
+                                   float* mean, float* invstd,
+                                   float* running_mean, float* running_var,
+                                   int64_t M, float eps, float momentum,
+                                   hipStream_t s) {
+  const int cg = chan_group(C);
+  const int cw = cg < 16 ? cg : 16;
+  hipLaunchKernelGGL(bn_det_finish_kernel, dim3((C + cw - 1) / cw),
+                     dim3(kBlock), 0, s, ws, G, C, cw, out, mean, invstd,
+                     running_mean, running_var, M, eps, momentum);
 }
 
 extern "C" void mine_bn_finalize(const float* sums, float* mean, float* invstd,

@@ -76,7 +76,11 @@ __device__ __forceinline__ int src_coord(int p, int r, int SA, int SB,
 // decoder's 2048-channel base convs run at M=384 pixels, 24 blocks
 // without it); slices atomically accumulate into an fp32 workspace
 // that igemm_epilogue_kernel then bias-adds and casts.
-template <int Sdim, int RS, int PAD, bool SPLIT>
+// DET (with SPLIT): slice z instead stores its fp32 tile with plain
+// stores into ws_out[z][M][K] (no zero fill needed: every slice writes
+// every valid element of its tile) and igemm_epilogue_det_kernel adds the
+// slices in ascending z. Same splitz, same kc_begin/kc_end.
+template <int Sdim, int RS, int PAD, bool SPLIT, bool DET>
 __global__ void __launch_bounds__(kBlock)
 conv_igemm_fwd_kernel(const __hip_bfloat16* __restrict__ x,  // (N,Hs,Ws,C)
                       const __hip_bfloat16* __restrict__ wp, // packed frags
@@ -165,7 +169,9 @@ conv_igemm_fwd_kernel(const __hip_bfloat16* __restrict__ x,  // (N,Hs,Ws,C)
     for (int rr = 0; rr < 4; ++rr) {
       const int64_t mm = m_out + rr;
       if (mm < M) {
-        if (SPLIT) {
+        if (SPLIT && DET) {
+          ws_out[((int64_t)blockIdx.z * M + mm) * K + kout] = acc[a][rr];
+        } else if (SPLIT) {
           atomicAdd(&ws_out[mm * K + kout], acc[a][rr]);
         } else {
           out[mm * K + kout] = (__hip_bfloat16)(acc[a][rr] + b);
@@ -184,6 +190,21 @@ igemm_epilogue_kernel(const float* __restrict__ ws,
   if (i >= total) return;
   const float b = bias ? bias[(int)(i % K)] : 0.0f;
   out[i] = (__hip_bfloat16)(ws[i] + b);
+}
+
+// deterministic split-K epilogue over ws[splitz][M][K]: adds the slices
+// in ascending z, then the bias, then casts
+__global__ void __launch_bounds__(kBlock)
+igemm_epilogue_det_kernel(const float* __restrict__ ws,
+                          const float* __restrict__ bias,
+                          __hip_bfloat16* __restrict__ out, int64_t total,
+                          int K, int splitz) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= total) return;
+  float acc = ws[i];
+  for (int z = 1; z < splitz; ++z) acc += ws[(int64_t)z * total + i];
+  const float b = bias ? bias[(int)(i % K)] : 0.0f;
+  out[i] = (__hip_bfloat16)(acc + b);
 }
 
 // ---------------------------------------------------------------------------
@@ -210,7 +231,11 @@ __device__ __forceinline__ bf16x8 frag32(const __hip_bfloat16* base) {
   return __builtin_bit_cast(bf16x8, s);
 }
 
-template <int Sdim, int PAD>
+// DET: `dw` is the workspace ws[n_slabs][K][C][RS]; each block stores its
+// 16x16 tile of slab `slab` with plain stores (every valid element of
+// every slab is written, so no zero fill), and igemm_wrw_finish_kernel
+// adds the slabs in ascending order. Same slab count and m_begin/m_end.
+template <int Sdim, int PAD, bool DET>
 __global__ void __launch_bounds__(64)
 conv_igemm_wrw_kernel(const __hip_bfloat16* __restrict__ x,   // (N,Hs,Ws,C)
                       const __hip_bfloat16* __restrict__ gy,  // (M,K) flat
@@ -296,10 +321,28 @@ conv_igemm_wrw_kernel(const __hip_bfloat16* __restrict__ x,   // (N,Hs,Ws,C)
     for (int rr = 0; rr < 4; ++rr) {
       const int kk = k0 + (lane >> 4) * 4 + rr;
       if (kk < K) {
-        atomicAdd(&dw[((int64_t)kk * C + cc) * RS + tap], acc[rr]);
+        const int64_t idx = ((int64_t)kk * C + cc) * RS + tap;
+        if (DET) {
+          dw[(int64_t)slab * K * C * RS + idx] = acc[rr];
+        } else {
+          atomicAdd(&dw[idx], acc[rr]);
+        }
       }
     }
   }
+}
+
+// deterministic weight-grad finish (after conv3x3_wrw_finish_kernel in
+// wrw_kernels.hip): dw[i] = ws[0][i] + ws[1][i] + ... in ascending slab
+// order, one thread per weight element.
+__global__ void __launch_bounds__(kBlock)
+igemm_wrw_finish_kernel(const float* __restrict__ ws, float* __restrict__ dw,
+                        int64_t n, int n_slabs) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  float acc = ws[i];
+  for (int sl = 1; sl < n_slabs; ++sl) acc += ws[(int64_t)sl * n + i];
+  dw[i] = acc;
 }
 
 // ---------------------------------------------------------------------------
@@ -350,25 +393,29 @@ extern "C" void mine_pack_gather(const void* w, const int* lut, void* out,
     KERNEL_CALL;                                                          \
   }
 
-// splitz > 1 requires ws (pre-zeroed fp32 (M,K)); the epilogue launch
-// bias-adds and casts into out.
+// splitz > 1 requires ws: pre-zeroed fp32 (M,K), or with det an
+// unfilled fp32 (splitz,M,K); the epilogue launch adds the bias (det: and
+// the slices, in ascending order) and casts into out.
 extern "C" void mine_conv_igemm_fwd(
     const void* x, const void* wp, const float* bias, void* out, float* ws,
     int64_t M, int P, int Q, int K, int Hs, int Ws, int C,
     int R, int S, int SA, int SB, int SD, int SE, int pad_mode, int splitz,
-    hipStream_t stream) {
+    int det, hipStream_t stream) {
   const dim3 grid((unsigned)((M + 63) / 64), (unsigned)((K + 63) / 64),
                   (unsigned)(splitz > 1 ? splitz : 1));
-#define CALL_FWD(SPLIT)                                                  \
-  hipLaunchKernelGGL((conv_igemm_fwd_kernel<Sdim, RS, PAD, SPLIT>),      \
+#define CALL_FWD(SPLIT, DET)                                             \
+  hipLaunchKernelGGL((conv_igemm_fwd_kernel<Sdim, RS, PAD, SPLIT, DET>), \
                      grid, dim3(kBlock), 0, stream,                      \
                      reinterpret_cast<const __hip_bfloat16*>(x),         \
                      reinterpret_cast<const __hip_bfloat16*>(wp), bias,  \
                      reinterpret_cast<__hip_bfloat16*>(out), ws,         \
                      M, P, Q, K, Hs, Ws, C, SA, SB, SD, SE)
 #define CALL_FWD_EITHER                                                  \
-  do { if (splitz > 1) { CALL_FWD(true); } else { CALL_FWD(false); } }   \
-  while (0)
+  do {                                                                   \
+    if (splitz > 1 && det) { CALL_FWD(true, true); }                     \
+    else if (splitz > 1) { CALL_FWD(true, false); }                      \
+    else { CALL_FWD(false, false); }                                     \
+  } while (0)
   if (R == 1 && S == 1) {
     IGEMM_DISPATCH_RS(1, 1, pad_mode, CALL_FWD_EITHER)
   } else if (R == 3 && S == 3) {
@@ -378,20 +425,25 @@ extern "C" void mine_conv_igemm_fwd(
   }
   if (splitz > 1) {
     const int64_t total = M * K;
-    hipLaunchKernelGGL(igemm_epilogue_kernel,
-                       dim3((unsigned)((total + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, stream, ws, bias,
-                       reinterpret_cast<__hip_bfloat16*>(out), total, K);
+    const dim3 egrid((unsigned)((total + kBlock - 1) / kBlock));
+    if (det)
+      hipLaunchKernelGGL(igemm_epilogue_det_kernel, egrid, dim3(kBlock), 0,
+                         stream, ws, bias,
+                         reinterpret_cast<__hip_bfloat16*>(out), total, K,
+                         splitz);
+    else
+      hipLaunchKernelGGL(igemm_epilogue_kernel, egrid, dim3(kBlock), 0,
+                         stream, ws, bias,
+                         reinterpret_cast<__hip_bfloat16*>(out), total, K);
   }
 #undef CALL_FWD_EITHER
 #undef CALL_FWD
 }
 
-extern "C" void mine_conv_igemm_wrw(
-    const void* x, const void* gy, float* dw,
-    int64_t M, int P, int Q, int K, int Hs, int Ws, int C,
-    int R, int S, int SA, int SB, int SD, int SE, int pad_mode,
-    hipStream_t stream) {
+// pixel slabs of the weight gradient (grid.x); the deterministic mode's
+// workspace holds that many (K,C,R,S) partials
+extern "C" int mine_conv_igemm_wrw_slabs(int64_t M, int K, int C, int R,
+                                         int S) {
   const int cg = (C + 15) / 16;
   const int kc = (K + 15) / 16;
   // fill the chip: ~1024 blocks if the work allows
@@ -399,13 +451,32 @@ extern "C" void mine_conv_igemm_wrw(
   const int64_t chunks = (M + 31) / 32;
   if (slabs > chunks) slabs = (int)chunks;
   if (slabs < 1) slabs = 1;
+  return slabs;
+}
+
+// ws_det == nullptr: atomics into the pre-zeroed dw. Otherwise the
+// deterministic pair: tiles into ws_det (slabs,K,C,R,S), unfilled, then
+// the finishing kernel writes dw (unfilled too).
+extern "C" void mine_conv_igemm_wrw(
+    const void* x, const void* gy, float* dw, float* ws_det,
+    int64_t M, int P, int Q, int K, int Hs, int Ws, int C,
+    int R, int S, int SA, int SB, int SD, int SE, int pad_mode,
+    hipStream_t stream) {
+  const int cg = (C + 15) / 16;
+  const int kc = (K + 15) / 16;
+  const int slabs = mine_conv_igemm_wrw_slabs(M, K, C, R, S);
   const dim3 grid((unsigned)slabs, (unsigned)kc, (unsigned)(cg * R * S));
-#define CALL_WRW                                                         \
-  hipLaunchKernelGGL((conv_igemm_wrw_kernel<Sdim, PAD>), grid,           \
+#define CALL_WRW_T(DET, DST)                                             \
+  hipLaunchKernelGGL((conv_igemm_wrw_kernel<Sdim, PAD, DET>), grid,      \
                      dim3(64), 0, stream,                                \
                      reinterpret_cast<const __hip_bfloat16*>(x),         \
-                     reinterpret_cast<const __hip_bfloat16*>(gy), dw,    \
+                     reinterpret_cast<const __hip_bfloat16*>(gy), DST,   \
                      M, P, Q, K, Hs, Ws, C, R * S, SA, SB, SD, SE, slabs)
+#define CALL_WRW                                                         \
+  do {                                                                   \
+    if (ws_det) { CALL_WRW_T(true, ws_det); }                            \
+    else { CALL_WRW_T(false, dw); }                                      \
+  } while (0)
   if (R == 1 && S == 1) {
     IGEMM_DISPATCH_RS(1, 1, pad_mode, CALL_WRW)
   } else if (R == 3 && S == 3) {
@@ -414,4 +485,11 @@ extern "C" void mine_conv_igemm_wrw(
     IGEMM_DISPATCH_RS(7, 49, pad_mode, CALL_WRW)
   }
 #undef CALL_WRW
+#undef CALL_WRW_T
+  if (ws_det) {
+    const int64_t n = (int64_t)K * C * R * S;
+    hipLaunchKernelGGL(igemm_wrw_finish_kernel,
+                       dim3((unsigned)((n + kBlock - 1) / kBlock)),
+                       dim3(kBlock), 0, stream, ws_det, dw, n, slabs);
+  }
 }
