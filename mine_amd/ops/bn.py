@@ -1,6 +1,6 @@
 """Fused BatchNorm + activation on the HIP kernels.
 
-Training-mode BN with fp32 statistics over bf16 (or fp32) channels_last
+Training-mode BN with fp32 statistics over bf16, fp16 (or fp32) channels_last
 activations, with the following activation fused into the normalize pass
 (and its derivative into the backward): none / relu / lrelu(0.1) / elu /
 add_relu (the ResNet residual join y = relu(bn(x) + res)).
@@ -69,8 +69,9 @@ class _JoinStatsFn(torch.autograd.Function):
     """x = (y_base[b] + bias[b,s]) + y_dec[b,s] with the per-channel
     (sum, sumsq) of x from the same pass (bn_join_stats_vec_kernel).
 
-    y_dec (B*S,K,H,W) and y_base (B,K,H,W) are bf16 channels_last, bias is
-    bf16 (B*S,K). x is bit-identical to the eager bf16 chain."""
+    y_dec (B*S,K,H,W) and y_base (B,K,H,W) are channels_last and bias is
+    (B*S,K), all bf16 or all fp16. x is bit-identical to the eager chain in
+    that dtype."""
 
     @staticmethod
     def forward(ctx, y_dec, y_base, bias, B, S):
@@ -95,11 +96,12 @@ class _JoinStatsFn(torch.autograd.Function):
 
 
 def join_stats_usable(y_dec: torch.Tensor, y_base: torch.Tensor) -> bool:
-    """True where the fused join kernel applies: bf16 channels_last on the
-    GPU with a 16-byte channel vector; everything else joins eagerly."""
+    """True where the fused join kernel applies: bf16 or fp16 channels_last
+    on the GPU with a 16-byte channel vector; everything else joins
+    eagerly."""
     return (y_dec.is_cuda and y_dec.dim() == 4
-            and y_dec.dtype == torch.bfloat16
-            and y_base.dtype == torch.bfloat16
+            and y_dec.dtype in (torch.bfloat16, torch.float16)
+            and y_base.dtype == y_dec.dtype
             and y_dec.shape[1] % 8 == 0
             and y_dec.is_contiguous(memory_format=torch.channels_last)
             and y_base.is_contiguous(memory_format=torch.channels_last))
@@ -108,7 +110,7 @@ def join_stats_usable(y_dec: torch.Tensor, y_base: torch.Tensor) -> bool:
 def join_stats(y_dec, y_base, bias, B: int, S: int):
     """Fused SplitConvBlock join; returns (x, sums) with sums the (2C,)
     fp32 buffer `FusedBNAct.forward(x, sums=sums)` consumes."""
-    return _JoinStatsFn.apply(y_dec, y_base, bias.to(torch.bfloat16), B, S)
+    return _JoinStatsFn.apply(y_dec, y_base, bias.to(y_dec.dtype), B, S)
 
 
 def _act_eager(act: str, z: torch.Tensor) -> torch.Tensor:
@@ -160,7 +162,7 @@ class FusedBNAct(nn.BatchNorm2d):
         assert (res is not None) == (self.act == "add_relu")
         use_kernel = (
             x.is_cuda and x.dim() == 4
-            and x.dtype in (torch.float32, torch.bfloat16)
+            and x.dtype in (torch.float32, torch.bfloat16, torch.float16)
             and x.is_contiguous(memory_format=torch.channels_last)
             and (res is None or (res.dtype == x.dtype and res.is_contiguous(
                 memory_format=torch.channels_last)))

@@ -2,9 +2,11 @@
 
 Carries the decoder's ConvBlock / Conv3x3 convolutions (the reference's
 ReflectionPad2d(1) + 3x3 nn.Conv2d, ref network/monodepth2/
-layers.py:106-138) on hand-written v_mfma_f32_16x16x32_bf16 tiles.
+layers.py:106-138) on hand-written v_mfma_f32_16x16x32_{bf16,f16}
+tiles: bf16 and fp16 activations run the same kernels, instantiated per
+element type, and the weights are packed in the activation's dtype.
 
-Forward runs the hand-written v_mfma_f32_16x16x32_bf16 kernel
+Forward runs the hand-written MFMA kernel
 (ops/csrc/conv_kernels.hip) with the pad folded into the LDS stage — no
 padded tensor is ever materialized. Backward is hand-written too:
 dW (and the bias gradient, in the same pass) on the MFMA wrw kernel
@@ -96,26 +98,37 @@ def _pack_lut_bwd(K: int, C: int, device) -> torch.Tensor:
     return lut
 
 
-def _gather(w: torch.Tensor, lut: torch.Tensor) -> torch.Tensor:
-    if w.is_cuda and w.dtype in (torch.float32, torch.bfloat16):
+_ELEM16 = (torch.bfloat16, torch.float16)  # element types of the kernels
+
+
+def _gather(w: torch.Tensor, lut: torch.Tensor,
+            dtype: torch.dtype) -> torch.Tensor:
+    if dtype not in _ELEM16:
+        raise ValueError(f"pack dtype must be bf16 or fp16, got {dtype}")
+    if w.is_cuda and w.dtype in (torch.float32,) + _ELEM16:
         ext = get_extension(required=True)
-        return ext.conv3x3_pack(w.detach().contiguous().reshape(-1), lut)
-    flat = torch.cat((w.reshape(-1), w.new_zeros(1))).to(torch.bfloat16)
+        return ext.conv3x3_pack(w.detach().contiguous().reshape(-1), lut,
+                                dtype)
+    flat = torch.cat((w.reshape(-1), w.new_zeros(1))).to(dtype)
     return flat[lut].contiguous()
 
 
-def pack_weights(w: torch.Tensor, flip: bool = False) -> torch.Tensor:
-    """(K, C, 3, 3) -> fragment-ordered bf16 buffer (one gather kernel on
-    the GPU; index arithmetic on the CPU)."""
+def pack_weights(w: torch.Tensor, flip: bool = False,
+                 dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """(K, C, 3, 3) -> fragment-ordered buffer of `dtype` (bf16 or fp16;
+    one gather kernel on the GPU, index arithmetic on the CPU). The A/B
+    lane maps of the bf16 and f16 MFMA are the same, so one LUT serves
+    both."""
     K, C = w.shape[0], w.shape[1]
-    return _gather(w, _pack_lut(K, C, flip, w.device))
+    return _gather(w, _pack_lut(K, C, flip, w.device), dtype)
 
 
-def pack_weights_bwd(w: torch.Tensor) -> torch.Tensor:
-    """(K, C, 3, 3) -> fragment-ordered bf16 buffer of the data
-    gradient's (C, ceil8(K), 3, 3) transposed, flipped weight."""
+def pack_weights_bwd(w: torch.Tensor,
+                     dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """(K, C, 3, 3) -> fragment-ordered buffer of `dtype` holding the
+    data gradient's (C, ceil8(K), 3, 3) transposed, flipped weight."""
     K, C = w.shape[0], w.shape[1]
-    return _gather(w, _pack_lut_bwd(K, C, w.device))
+    return _gather(w, _pack_lut_bwd(K, C, w.device), dtype)
 
 
 def bias_grad(gy: torch.Tensor) -> torch.Tensor:
@@ -124,8 +137,8 @@ def bias_grad(gy: torch.Tensor) -> torch.Tensor:
     The fused conv's backward gets its bias gradient from the wrw kernel
     (ext.conv3x3_wrw_bias); this is the stand-alone form.
 
-    On the GPU in bf16 this is the BN statistics kernel's sum half: it
-    reads the bf16 gradient once at stream rate and makes no fp32 copy.
+    On the GPU in bf16 / fp16 this is the BN statistics kernel's sum
+    half: it reads the gradient once at stream rate and makes no fp32 copy.
     Like every BN statistic it combines per-block partials with fp32
     atomics, so the last bits depend on the order the blocks finish in;
     in deterministic mode (ops.backend) it takes the order-fixed kernels.
@@ -133,7 +146,7 @@ def bias_grad(gy: torch.Tensor) -> torch.Tensor:
     """
     B, K, H, W = gy.shape
     M = B * H * W
-    if (gy.is_cuda and gy.dtype == torch.bfloat16
+    if (gy.is_cuda and gy.dtype in _ELEM16
             and gy.is_contiguous(memory_format=torch.channels_last)):
         ext = get_extension(required=True)
         flat = gy.permute(0, 2, 3, 1).reshape(-1)
@@ -173,7 +186,7 @@ class _Conv3x3ReflFn(torch.autograd.Function):
         ext = get_extension(required=True)
         B, C, H, W = x.shape
         K = w.shape[0]
-        wp = pack_weights(w)
+        wp = pack_weights(w, dtype=x.dtype)
         x_flat = x.permute(0, 2, 3, 1).reshape(-1)  # NHWC view
         out = torch.empty(B * H * W * K, device=x.device, dtype=x.dtype)
         ext.conv3x3_fwd(x_flat, wp,
@@ -203,7 +216,7 @@ class _Conv3x3ReflFn(torch.autograd.Function):
         if _bwd_mode() == "hip":
             ext = get_extension(required=True)
             # dW on the MFMA wrw kernel (fp32 accumulate); reads the
-            # unpadded bf16 x with the reflect staged in LDS. The bias
+            # unpadded x with the reflect staged in LDS. The bias
             # gradient comes out of the same pass over gy.
             x_flat = xs.permute(0, 2, 3, 1).reshape(-1)
             gy_flat = gy.permute(0, 2, 3, 1).reshape(-1)
@@ -232,28 +245,23 @@ class _Conv3x3ReflFn(torch.autograd.Function):
 def conv3x3_reflect(x: torch.Tensor, w: torch.Tensor,
                     bias: torch.Tensor = None) -> torch.Tensor:
     """Reflection-pad(1) + 3x3 stride-1 conv. MFMA fast path on GPU
-    bf16 channels_last with C % 8 == 0; eager fallback otherwise."""
+    bf16 / fp16 channels_last with C % 8 == 0; eager fallback otherwise."""
     # Profitability gate (measured on MI355X): the 64-pixel row tile wins
     # for small-channel wide images (the decoder's full/half-res blocks,
     # 4.2x vs pad+MIOpen at 256x16x256x384); for C>64 or narrow images
     # MIOpen's tuned igemm is better and the pad recompute in backward
     # is not paid back.
-    if x.is_cuda and x.dtype == torch.float16:
-        # fp16 configs (Flowers, driver config 5): the MFMA kernels are
-        # bf16; one cast pass each way beats the library fp16 path and
-        # its per-shape find cost. Accumulation is fp32 either way.
-        return conv3x3_reflect(x.to(torch.bfloat16), w, bias).to(torch.float16)
     # (C % 16: the wrw kernel's c-groups are 16-wide. C <= 64: at C=128
     # the 101 KiB LDS stage drops occupancy to one workgroup per CU and
     # measured slower than the library igemm — the C=128 wide blocks
     # stay on the library path until a bandwidth-tiled variant exists.)
-    usable = (x.is_cuda and x.dtype == torch.bfloat16
+    usable = (x.is_cuda and x.dtype in _ELEM16
               and x.shape[1] % 16 == 0 and x.shape[1] <= 64
               and x.shape[-1] >= 48 and x.shape[-2] >= 8
               and x.is_contiguous(memory_format=torch.channels_last))
     if usable:
         return _Conv3x3ReflFn.apply(x, w, bias)
-    if x.is_cuda and x.dtype == torch.bfloat16 and (
+    if x.is_cuda and x.dtype in _ELEM16 and (
             _FORCE_IGEMM or is_deterministic()
             or x.numel() * 2 <= 1 << 25):
         # small (L2/L3-resident) narrow-image shapes, e.g. the 256-ch
@@ -277,8 +285,8 @@ def conv3x3_bwd_data(gy: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     tests/test_gpu_ops.py. rot180 and the swap live in the pack LUT
     (_pack_lut_bwd), not in a copy of the weight.
 
-    gy: (B, K, H, W) bf16 channels_last; w: (K, C, 3, 3). Returns
-    gx (B, C, H, W) bf16 channels_last.
+    gy: (B, K, H, W) bf16 or fp16 channels_last; w: (K, C, 3, 3). Returns
+    gx (B, C, H, W) channels_last in gy's dtype.
     """
     ext = get_extension(required=True)
     B, K, H, W = gy.shape
@@ -293,11 +301,11 @@ def conv3x3_bwd_data(gy: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
             (gy, gy.new_zeros(B, Kp - K, H, W)), dim=1
         ).contiguous(memory_format=torch.channels_last)
     c_mem = 4 if K == 4 else Kp
-    wp = pack_weights_bwd(w)
+    wp = pack_weights_bwd(w, dtype=gy.dtype)
     gy_flat = gy.permute(0, 2, 3, 1).reshape(-1)
     # logical image = gy zero-embedded by 1 ring -> output (H+2, W+2, C)
     gxp = torch.empty(B * (H + 2) * (W + 2) * C, device=gy.device,
-                      dtype=torch.bfloat16)
+                      dtype=gy.dtype)
     ext.conv3x3_fwd(gy_flat, wp,
                     torch.empty(0, device=gy.device, dtype=torch.float32),
                     gxp, B, H + 2, W + 2, Kp, C, 1, H, W, 1, c_mem)

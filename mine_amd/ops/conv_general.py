@@ -5,7 +5,8 @@ Carries the ResNet-50 stack (ref network/monodepth2/resnet_encoder.py:
 the decoder's receptive-field neck (ref depth_decoder.py:56-61) and the
 SplitConvBlock base convs (reflect-padded 3x3, ref monodepth2/
 layers.py:123-138) on the hand-written igemm kernels
-(ops/csrc/igemm_kernels.hip) — forward, data-grad and weight-grad.
+(ops/csrc/igemm_kernels.hip) — forward, data-grad and weight-grad, in
+bf16 or fp16 (the weights are packed in the activation's dtype).
 These shapes are tiny (batch 4, L2-resident) and were launch-bound on
 the library path; see the kernel header for the design.
 
@@ -70,10 +71,11 @@ def _frag_lut(K_log: int, C_log: int, R: int, S: int, C_phys: int,
     return lut
 
 
-def pack_weights_general(w: torch.Tensor, trans: bool = False) -> torch.Tensor:
-    """(K, C, R, S) contiguous -> fragment-ordered bf16 buffer (one
-    launch). trans packs the transposed (C-major) logical layout for the
-    data-grad."""
+def pack_weights_general(w: torch.Tensor, trans: bool = False,
+                         dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """(K, C, R, S) contiguous -> fragment-ordered buffer of `dtype`
+    (bf16 or fp16; one launch). trans packs the transposed (C-major)
+    logical layout for the data-grad."""
     ext = get_extension(required=True)
     K, C, R, S = w.shape
     Cp = (C + 7) & ~7
@@ -82,7 +84,7 @@ def pack_weights_general(w: torch.Tensor, trans: bool = False) -> torch.Tensor:
         lut = _frag_lut(Cp, Kp, R, S, C, K, C, True, w.device)
     else:
         lut = _frag_lut(K, Cp, R, S, C, K, C, False, w.device)
-    return ext.pack_gather(w.reshape(-1), lut)
+    return ext.pack_gather(w.reshape(-1), lut, dtype)
 
 
 class _ConvIgemmFn(torch.autograd.Function):
@@ -100,7 +102,7 @@ class _ConvIgemmFn(torch.autograd.Function):
         else:
             P = (Hs + 2 * pad - R) // stride + 1
             Q = (Ws + 2 * pad - S) // stride + 1
-        wp = pack_weights_general(w)
+        wp = pack_weights_general(w, dtype=x.dtype)
         M = B * P * Q
         # read once: backward uses the mode the graph was built in
         det = is_deterministic()
@@ -147,7 +149,7 @@ class _ConvIgemmFn(torch.autograd.Function):
         if ctx.has_bias:
             gb = gy.float().sum((0, 2, 3)).to(w.dtype)
         if ctx.needs_input_grad[0]:
-            wtp = pack_weights_general(w, trans=True)
+            wtp = pack_weights_general(w, trans=True, dtype=gy.dtype)
             empty = torch.empty(0, device=x.device, dtype=torch.float32)
             if reflect:
                 # grad to the (virtually) padded input, then reflect-fold
@@ -180,12 +182,7 @@ def conv2d_mfma(x: torch.Tensor, w: torch.Tensor,
         # the library (and a reflect conv through eager F.pad, whose
         # backward sums with atomics). Deterministic mode keeps it here.
         w = w.contiguous()
-    if x.is_cuda and x.dtype == torch.float16 and (R, S) in (
-            (1, 1), (3, 3), (7, 7)) and (not reflect or stride == 1):
-        # fp16 configs: cast through the bf16 MFMA path (see conv.py)
-        return conv2d_mfma(x.to(torch.bfloat16), w, bias, stride, padding,
-                           reflect).to(torch.float16)
-    usable = (x.is_cuda and x.dtype == torch.bfloat16
+    usable = (x.is_cuda and x.dtype in (torch.bfloat16, torch.float16)
               and (R, S) in ((1, 1), (3, 3), (7, 7))
               and w.is_contiguous()
               and x.is_contiguous(memory_format=torch.channels_last)

@@ -28,18 +28,19 @@ void mine_tgt_composite_bwd(const float*, const float*, const float*,
                             int, int, int, int, int, int, int, hipStream_t);
 void mine_conv_igemm_fwd(const void*, const void*, const float*, void*,
                          float*, int64_t, int, int, int, int, int, int, int,
-                         int, int, int, int, int, int, int, int, hipStream_t);
+                         int, int, int, int, int, int, int, int, int,
+                         hipStream_t);
 int mine_conv_igemm_wrw_slabs(int64_t, int, int, int, int);
 void mine_conv_igemm_wrw(const void*, const void*, float*, float*, int64_t,
                          int, int, int, int, int, int, int, int, int, int,
-                         int, int, int, hipStream_t);
+                         int, int, int, int, hipStream_t);
 void mine_eav2_fwd(const float*, const float*, const float*, float*, int,
                    int, int, int64_t, int64_t, int64_t, int64_t,
                    hipStream_t);
 void mine_eav2_bwd(const float*, const float*, const float*, float*, float*,
                    const float*, float*, int, int, int, int64_t, int64_t,
                    int64_t, int64_t, hipStream_t);
-void mine_pack_gather(const void*, const int*, void*, int64_t, int,
+void mine_pack_gather(const void*, const int*, void*, int64_t, int, int,
                       hipStream_t);
 void mine_upsample2x_fwd(const void*, void*, int64_t, int64_t, int64_t,
                          int64_t, int, hipStream_t);
@@ -49,19 +50,26 @@ void mine_reflect_pad_fwd_f32(const float*, float*, int, int, int, int, int,
                               hipStream_t);
 void mine_reflect_pad_fwd_bf16(const void*, void*, int, int, int, int, int,
                                hipStream_t);
+void mine_reflect_pad_fwd_f16(const void*, void*, int, int, int, int, int,
+                              hipStream_t);
+void mine_reflect_pad_bwd_f16(const void*, void*, int, int, int, int, int,
+                              hipStream_t);
 void mine_reflect_pad_bwd_f32(const float*, float*, int, int, int, int, int,
                               hipStream_t);
 void mine_reflect_pad_bwd_bf16(const void*, void*, int, int, int, int, int,
                                hipStream_t);
 int mine_conv3x3_fwd(const void*, const void*, const float*, void*, int, int,
-                     int, int, int, int, int, int, int, int, hipStream_t);
-void mine_conv3x3_pack(const void*, int, const int64_t*, void*, int64_t,
+                     int, int, int, int, int, int, int, int, int, hipStream_t);
+void mine_conv3x3_pack(const void*, int, const int64_t*, void*, int, int64_t,
                        int64_t, hipStream_t);
 void mine_conv3x3_wrw_plan(int, int, int64_t, int, int*, int*, int64_t*);
 int mine_conv3x3_wrw(const void*, const void*, float*, float*, float*, int,
-                     int, int, int, int, int, int, hipStream_t);
+                     int, int, int, int, int, int, int, hipStream_t);
 void mine_mpi_head_fwd_f32(const void*, float*, int64_t, int, hipStream_t);
 void mine_mpi_head_fwd_bf16(const void*, float*, int64_t, int, hipStream_t);
+void mine_mpi_head_fwd_f16(const void*, float*, int64_t, int, hipStream_t);
+void mine_mpi_head_bwd_f16(const void*, const float*, void*, int64_t, int,
+                           hipStream_t);
 void mine_mpi_head_bwd_f32(const void*, const float*, void*, int64_t, int,
                            hipStream_t);
 void mine_mpi_head_bwd_bf16(const void*, const float*, void*, int64_t, int,
@@ -70,6 +78,9 @@ void mine_bn_stats_f32(const void*, float*, int64_t, int, int, int,
                        hipStream_t);
 void mine_bn_stats_bf16(const void*, float*, int64_t, int, int, int,
                         hipStream_t);
+void mine_bn_stats_f16(const void*, float*, int64_t, int, int, int,
+                       hipStream_t);
+int mine_bn_reduce_grid_f16(int64_t, int, int);
 int mine_bn_reduce_grid_f32(int64_t, int, int);
 int mine_bn_reduce_grid_bf16(int64_t, int, int);
 void mine_bn_det_finish(const float*, int, int, float*, float*, float*,
@@ -77,6 +88,9 @@ void mine_bn_det_finish(const float*, int, int, float*, float*, float*,
 void mine_bn_join_stats_bf16(const void*, const void*, const void*, void*,
                              float*, int64_t, int, int, int, int, int,
                              hipStream_t);
+void mine_bn_join_stats_f16(const void*, const void*, const void*, void*,
+                            float*, int64_t, int, int, int, int, int,
+                            hipStream_t);
 void mine_bn_finalize(const float*, float*, float*, float*, float*, int64_t,
                       int, float, float, hipStream_t);
 void mine_bn_act_fwd_f32(const void*, const void*, const float*, const float*,
@@ -85,6 +99,17 @@ void mine_bn_act_fwd_f32(const void*, const void*, const float*, const float*,
 void mine_bn_act_fwd_bf16(const void*, const void*, const float*, const float*,
                           const float*, const float*, void*, int64_t, int, int,
                           int, hipStream_t);
+void mine_bn_act_fwd_f16(const void*, const void*, const float*, const float*,
+                         const float*, const float*, void*, int64_t, int, int,
+                         int, hipStream_t);
+void mine_bn_act_bwd_reduce_f16(const void*, const void*, const void*,
+                                const float*, const float*, const float*,
+                                const float*, float*, int64_t, int, int, int,
+                                int, hipStream_t);
+void mine_bn_act_bwd_dx_f16(const void*, const void*, const void*,
+                            const float*, const float*, const float*,
+                            const float*, const float*, void*, void*, int64_t,
+                            int, int, int, hipStream_t);
 void mine_bn_act_bwd_reduce_f32(const void*, const void*, const void*,
                                 const float*, const float*, const float*,
                                 const float*, float*, int64_t, int, int, int,
@@ -121,6 +146,24 @@ const float* optr(const at::Tensor& t) {
 
 hipStream_t stream() {
   return at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+}
+
+// the two 16-bit element types of the MFMA / stream kernels
+bool is_16bit(at::ScalarType t) {
+  return t == at::kBFloat16 || t == at::kHalf;
+}
+
+// weight dtype code of the pack kernels: 0 fp32, 1 bf16, 2 fp16
+int w_kind(at::ScalarType t) {
+  return t == at::kBFloat16 ? 1 : (t == at::kHalf ? 2 : 0);
+}
+
+// pack output dtype from the optional Python-side argument (default bf16)
+at::ScalarType pack_dtype(const c10::optional<at::ScalarType>& dtype,
+                          const char* who) {
+  const at::ScalarType t = dtype.value_or(at::kBFloat16);
+  TORCH_CHECK(is_16bit(t), who, ": output dtype must be bf16 or fp16");
+  return t;
 }
 
 std::vector<at::Tensor> src_composite_fwd(at::Tensor mpi, at::Tensor depths,
@@ -243,16 +286,19 @@ at::Tensor eav2_bwd(at::Tensor disp, at::Tensor img, at::Tensor mean_d,
   return grad;
 }
 
-// one-launch fragment pack: bf16 gather through a device LUT (neg -> 0)
-at::Tensor pack_gather(at::Tensor w, at::Tensor lut) {
+// one-launch fragment pack: gather through a device LUT (neg -> 0) into
+// bf16 (default) or fp16
+at::Tensor pack_gather(at::Tensor w, at::Tensor lut,
+                       c10::optional<at::ScalarType> dtype) {
   TORCH_CHECK(w.is_cuda() && w.is_contiguous() && lut.is_contiguous());
   TORCH_CHECK(lut.scalar_type() == at::kInt);
-  TORCH_CHECK(w.scalar_type() == at::kFloat ||
-              w.scalar_type() == at::kBFloat16);
-  auto out = at::empty({lut.numel()}, w.options().dtype(at::kBFloat16));
+  TORCH_CHECK(w.scalar_type() == at::kFloat || is_16bit(w.scalar_type()),
+              "pack_gather: weight must be f32, bf16 or fp16");
+  const at::ScalarType ot = pack_dtype(dtype, "pack_gather");
+  auto out = at::empty({lut.numel()}, w.options().dtype(ot));
   mine_pack_gather(w.data_ptr(), lut.data_ptr<int>(), out.data_ptr(),
-                   lut.numel(), w.scalar_type() == at::kFloat ? 1 : 0,
-                   stream());
+                   lut.numel(), w_kind(w.scalar_type()),
+                   ot == at::kHalf ? 1 : 0, stream());
   return out;
 }
 
@@ -263,8 +309,10 @@ at::Tensor conv_igemm_fwd(at::Tensor x_flat, at::Tensor wp, at::Tensor bias,
                           int64_t SE, int64_t pad_mode, bool deterministic) {
   TORCH_CHECK(x_flat.is_cuda() && x_flat.is_contiguous() &&
               wp.is_contiguous());
-  TORCH_CHECK(x_flat.scalar_type() == at::kBFloat16 &&
-              wp.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(is_16bit(x_flat.scalar_type()) &&
+              wp.scalar_type() == x_flat.scalar_type(),
+              "conv_igemm_fwd: x and the packed weights must both be bf16 or "
+              "both fp16");
   TORCH_CHECK(C % 8 == 0);
   auto out = at::empty({M * K}, x_flat.options());
   // contraction split-K when the (M, K) grid underfills the 256 CUs
@@ -291,7 +339,8 @@ at::Tensor conv_igemm_fwd(at::Tensor x_flat, at::Tensor wp, at::Tensor bias,
                       out.data_ptr(), ws_ptr, M, (int)P, (int)Q, (int)K,
                       (int)Hs, (int)Ws, (int)C, (int)R, (int)S, (int)SA,
                       (int)SB, (int)SD, (int)SE, (int)pad_mode, splitz,
-                      deterministic ? 1 : 0, stream());
+                      deterministic ? 1 : 0,
+                      x_flat.scalar_type() == at::kHalf ? 1 : 0, stream());
   return out;
 }
 
@@ -302,8 +351,9 @@ at::Tensor conv_igemm_wrw(at::Tensor x_flat, at::Tensor gy_flat, int64_t M,
                           int64_t pad_mode, bool deterministic) {
   TORCH_CHECK(x_flat.is_cuda() && x_flat.is_contiguous() &&
               gy_flat.is_contiguous());
-  TORCH_CHECK(x_flat.scalar_type() == at::kBFloat16 &&
-              gy_flat.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(is_16bit(x_flat.scalar_type()) &&
+              gy_flat.scalar_type() == x_flat.scalar_type(),
+              "conv_igemm_wrw: x and gy must both be bf16 or both fp16");
   const auto fopt = x_flat.options().dtype(at::kFloat);
   at::Tensor dw, ws;
   float* ws_ptr = nullptr;
@@ -320,23 +370,26 @@ at::Tensor conv_igemm_wrw(at::Tensor x_flat, at::Tensor gy_flat, int64_t M,
   mine_conv_igemm_wrw(x_flat.data_ptr(), gy_flat.data_ptr(),
                       dw.data_ptr<float>(), ws_ptr, M, (int)P, (int)Q, (int)K,
                       (int)Hs, (int)Ws, (int)C, (int)R, (int)S, (int)SA,
-                      (int)SB, (int)SD, (int)SE, (int)pad_mode, stream());
+                      (int)SB, (int)SD, (int)SE, (int)pad_mode,
+                      x_flat.scalar_type() == at::kHalf ? 1 : 0, stream());
   return dw;
 }
 
 // --------------------------------------------------------------------------
-// nearest x2 upsample — flat logical (N,H,W,C); bf16 needs C%8==0,
+// nearest x2 upsample — flat logical (N,H,W,C); bf16 / fp16 need C%8==0,
 // f32 C%4==0 (see resample_kernels.hip).
 
 at::Tensor upsample2x_fwd(at::Tensor in, int64_t N, int64_t H, int64_t W,
                           int64_t C) {
   TORCH_CHECK(in.is_cuda() && in.is_contiguous() &&
               in.numel() == N * H * W * C);
-  const bool bf16 = in.scalar_type() == at::kBFloat16;
-  TORCH_CHECK(bf16 ? (C % 8 == 0) : (C % 4 == 0));
+  const at::ScalarType t = in.scalar_type();
+  TORCH_CHECK(t == at::kFloat || is_16bit(t),
+              "upsample2x: dtype must be f32, bf16 or fp16");
+  TORCH_CHECK(is_16bit(t) ? (C % 8 == 0) : (C % 4 == 0));
   auto out = at::empty({N * H * W * 4 * C}, in.options());
-  mine_upsample2x_fwd(in.data_ptr(), out.data_ptr(), N, H, W, C,
-                      bf16 ? 1 : 0, stream());
+  mine_upsample2x_fwd(in.data_ptr(), out.data_ptr(), N, H, W, C, w_kind(t),
+                      stream());
   return out;
 }
 
@@ -344,11 +397,13 @@ at::Tensor upsample2x_bwd(at::Tensor gout, int64_t N, int64_t H, int64_t W,
                           int64_t C) {
   TORCH_CHECK(gout.is_cuda() && gout.is_contiguous() &&
               gout.numel() == N * H * W * 4 * C);
-  const bool bf16 = gout.scalar_type() == at::kBFloat16;
-  TORCH_CHECK(bf16 ? (C % 8 == 0) : (C % 4 == 0));
+  const at::ScalarType t = gout.scalar_type();
+  TORCH_CHECK(t == at::kFloat || is_16bit(t),
+              "upsample2x: dtype must be f32, bf16 or fp16");
+  TORCH_CHECK(is_16bit(t) ? (C % 8 == 0) : (C % 4 == 0));
   auto gin = at::empty({N * H * W * C}, gout.options());
-  mine_upsample2x_bwd(gout.data_ptr(), gin.data_ptr(), N, H, W, C,
-                      bf16 ? 1 : 0, stream());
+  mine_upsample2x_bwd(gout.data_ptr(), gin.data_ptr(), N, H, W, C, w_kind(t),
+                      stream());
   return gin;
 }
 
@@ -368,8 +423,11 @@ at::Tensor reflect_pad_fwd(at::Tensor in, int64_t N, int64_t H, int64_t W,
   } else if (in.scalar_type() == at::kBFloat16) {
     mine_reflect_pad_fwd_bf16(in.data_ptr(), out.data_ptr(),
                               N, H, W, C, pad, stream());
+  } else if (in.scalar_type() == at::kHalf) {
+    mine_reflect_pad_fwd_f16(in.data_ptr(), out.data_ptr(),
+                             N, H, W, C, pad, stream());
   } else {
-    TORCH_CHECK(false, "reflect_pad: dtype must be f32 or bf16");
+    TORCH_CHECK(false, "reflect_pad: dtype must be f32, bf16 or fp16");
   }
   return out;
 }
@@ -385,24 +443,29 @@ at::Tensor reflect_pad_bwd(at::Tensor gout, int64_t N, int64_t H, int64_t W,
   } else if (gout.scalar_type() == at::kBFloat16) {
     mine_reflect_pad_bwd_bf16(gout.data_ptr(), gin.data_ptr(),
                               N, H, W, C, pad, stream());
+  } else if (gout.scalar_type() == at::kHalf) {
+    mine_reflect_pad_bwd_f16(gout.data_ptr(), gin.data_ptr(),
+                             N, H, W, C, pad, stream());
   } else {
-    TORCH_CHECK(false, "reflect_pad: dtype must be f32 or bf16");
+    TORCH_CHECK(false, "reflect_pad: dtype must be f32, bf16 or fp16");
   }
   return gin;
 }
 
 // --------------------------------------------------------------------------
 // fused BatchNorm + activation (see bn_kernels.hip). Tensors arrive as
-// flat logical (M, C) channels_last views; f32 or bf16.
+// flat logical (M, C) channels_last views; f32, bf16 or fp16.
 
 #define BN_DISPATCH(FN, T, ...)                                   \
   do {                                                            \
     if ((T) == at::kFloat) FN##_f32(__VA_ARGS__);                 \
     else if ((T) == at::kBFloat16) FN##_bf16(__VA_ARGS__);        \
-    else TORCH_CHECK(false, "bn: dtype must be f32 or bf16");     \
+    else if ((T) == at::kHalf) FN##_f16(__VA_ARGS__);             \
+    else TORCH_CHECK(false, "bn: dtype must be f32, bf16 or fp16"); \
   } while (0)
 
-// fused reflect-pad + 3x3 conv (MFMA); flat NHWC views, bf16.
+// fused reflect-pad + 3x3 conv (MFMA); flat NHWC views, all bf16 or all
+// fp16.
 // (src_h, src_w, off) back a zero-embedded logical image for the
 // transposed/data-grad use (pad_mode 1, off 1, logical = src + 2);
 // plain forward: src == logical, off == 0.
@@ -416,9 +479,11 @@ void conv3x3_fwd(at::Tensor x_flat, at::Tensor wp, at::Tensor bias,
   if (c_mem == 0) c_mem = C;
   TORCH_CHECK(x_flat.is_cuda() && x_flat.is_contiguous() &&
               wp.is_contiguous() && out.is_contiguous());
-  TORCH_CHECK(x_flat.scalar_type() == at::kBFloat16 &&
-              wp.scalar_type() == at::kBFloat16 &&
-              out.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(is_16bit(x_flat.scalar_type()) &&
+              wp.scalar_type() == x_flat.scalar_type() &&
+              out.scalar_type() == x_flat.scalar_type(),
+              "conv3x3_fwd: x, the packed weights and out must all be bf16 "
+              "or all fp16");
   TORCH_CHECK(C % 8 == 0 && x_flat.numel() == N * src_h * src_w * c_mem);
   TORCH_CHECK(out.numel() == N * H * W * K);
   TORCH_CHECK(N > 0 && N <= 65535 && H > 0 && W > 0 && (H + 3) / 4 <= 65535);
@@ -434,30 +499,35 @@ void conv3x3_fwd(at::Tensor x_flat, at::Tensor wp, at::Tensor bias,
       x_flat.data_ptr(), wp.data_ptr(),
       bias.numel() ? bias.data_ptr<float>() : nullptr, out.data_ptr(), (int)N,
       (int)H, (int)W, (int)C, (int)c_mem, (int)K, (int)pad_mode, (int)src_h,
-      (int)src_w, (int)off, stream());
+      (int)src_w, (int)off, x_flat.scalar_type() == at::kHalf ? 1 : 0,
+      stream());
   TORCH_CHECK(rc == 0, "conv3x3_fwd: no kernel for C=", C, " c_mem=", c_mem,
               " pad_mode=", pad_mode);
 }
 
-// (K,C,3,3) weight (fp32 or bf16, flat) -> fragment-ordered bf16 buffer
-// through an int64 gather LUT; LUT entries == w.numel() read as zero.
-at::Tensor conv3x3_pack(at::Tensor w_flat, at::Tensor lut) {
+// (K,C,3,3) weight (fp32, bf16 or fp16, flat) -> fragment-ordered buffer
+// of `dtype` (bf16 by default, or fp16) through an int64 gather LUT; LUT
+// entries == w.numel() read as zero.
+at::Tensor conv3x3_pack(at::Tensor w_flat, at::Tensor lut,
+                        c10::optional<at::ScalarType> dtype) {
   TORCH_CHECK(w_flat.is_cuda() && w_flat.is_contiguous() && lut.is_cuda() &&
               lut.is_contiguous() && lut.scalar_type() == at::kLong);
   TORCH_CHECK(w_flat.scalar_type() == at::kFloat ||
-              w_flat.scalar_type() == at::kBFloat16,
-              "conv3x3_pack: weight must be f32 or bf16");
-  auto out = at::empty({lut.numel()}, w_flat.options().dtype(at::kBFloat16));
+              is_16bit(w_flat.scalar_type()),
+              "conv3x3_pack: weight must be f32, bf16 or fp16");
+  const at::ScalarType ot = pack_dtype(dtype, "conv3x3_pack");
+  auto out = at::empty({lut.numel()}, w_flat.options().dtype(ot));
   if (lut.numel())
-    mine_conv3x3_pack(w_flat.data_ptr(),
-                      w_flat.scalar_type() == at::kBFloat16 ? 1 : 0,
-                      lut.data_ptr<int64_t>(), out.data_ptr(), lut.numel(),
-                      w_flat.numel(), stream());
+    mine_conv3x3_pack(w_flat.data_ptr(), w_kind(w_flat.scalar_type()),
+                      lut.data_ptr<int64_t>(), out.data_ptr(),
+                      ot == at::kHalf ? 1 : 0, lut.numel(), w_flat.numel(),
+                      stream());
   return out;
 }
 
 // Weight (and bias) gradient of the fused reflect-pad 3x3 conv (see
-// wrw_kernels.hip). Flat NHWC bf16 inputs; returns dW fp32 (K, C, 3, 3)
+// wrw_kernels.hip). Flat NHWC inputs, both bf16 or both fp16; returns dW
+// fp32 (K, C, 3, 3)
 // and, with want_bias, db fp32 (K). Every workgroup writes its partial
 // to a workspace and a second kernel sums them in a fixed order, so the
 // result is bitwise reproducible. max_slabs caps the number of pixel
@@ -467,8 +537,9 @@ static std::tuple<at::Tensor, at::Tensor> wrw_impl(
     int64_t C, int64_t K, bool want_bias, int64_t max_slabs) {
   TORCH_CHECK(x_flat.is_cuda() && gy_flat.is_cuda() &&
               x_flat.is_contiguous() && gy_flat.is_contiguous());
-  TORCH_CHECK(x_flat.scalar_type() == at::kBFloat16 &&
-              gy_flat.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(is_16bit(x_flat.scalar_type()) &&
+              gy_flat.scalar_type() == x_flat.scalar_type(),
+              "conv3x3_wrw: x and gy must both be bf16 or both fp16");
   TORCH_CHECK(C % 16 == 0 && C >= 16 && C <= 64,
               "conv3x3_wrw: C must be 16, 32, 48 or 64, got ", C);
   TORCH_CHECK(K >= 1 && W >= 2 && H >= 2 && N >= 1 && max_slabs >= 0);
@@ -497,7 +568,8 @@ static std::tuple<at::Tensor, at::Tensor> wrw_impl(
   const int rc = mine_conv3x3_wrw(
       x_flat.data_ptr(), gy_flat.data_ptr(), ws.data_ptr<float>(),
       dw.data_ptr<float>(), want_bias ? db.data_ptr<float>() : nullptr,
-      (int)N, (int)H, (int)W, (int)C, (int)Kmem, (int)K, slabs, stream());
+      (int)N, (int)H, (int)W, (int)C, (int)Kmem, (int)K, slabs,
+      x_flat.scalar_type() == at::kHalf ? 1 : 0, stream());
   TORCH_CHECK(rc != -2, "conv3x3_wrw: kernel launch failed for C=", C,
               " K=", K);
   TORCH_CHECK(rc == 0, "conv3x3_wrw: no kernel for C=", C, " K=", K);
@@ -527,8 +599,11 @@ at::Tensor mpi_head_fwd(at::Tensor z, int64_t N, bool alpha) {
   else if (z.scalar_type() == at::kBFloat16)
     mine_mpi_head_fwd_bf16(z.data_ptr(), out.data_ptr<float>(), N,
                            alpha ? 1 : 0, stream());
+  else if (z.scalar_type() == at::kHalf)
+    mine_mpi_head_fwd_f16(z.data_ptr(), out.data_ptr<float>(), N,
+                          alpha ? 1 : 0, stream());
   else
-    TORCH_CHECK(false, "mpi_head: dtype must be f32 or bf16");
+    TORCH_CHECK(false, "mpi_head: dtype must be f32, bf16 or fp16");
   return out;
 }
 
@@ -538,6 +613,9 @@ at::Tensor mpi_head_bwd(at::Tensor z, at::Tensor gout, int64_t N, bool alpha) {
   if (z.scalar_type() == at::kFloat)
     mine_mpi_head_bwd_f32(z.data_ptr(), gout.data_ptr<float>(), gz.data_ptr(),
                           N, alpha ? 1 : 0, stream());
+  else if (z.scalar_type() == at::kHalf)
+    mine_mpi_head_bwd_f16(z.data_ptr(), gout.data_ptr<float>(),
+                          gz.data_ptr(), N, alpha ? 1 : 0, stream());
   else
     mine_mpi_head_bwd_bf16(z.data_ptr(), gout.data_ptr<float>(),
                            gz.data_ptr(), N, alpha ? 1 : 0, stream());
@@ -553,11 +631,12 @@ at::Tensor mpi_head_bwd(at::Tensor z, at::Tensor gout, int64_t N, bool alpha) {
 // mine_bn_det_finish adds them in a fixed order (bn_kernels.hip).
 int bn_reduce_grid(at::ScalarType t, int64_t M, int64_t C,
                    int64_t max_blocks) {
-  TORCH_CHECK(t == at::kFloat || t == at::kBFloat16,
-              "bn: dtype must be f32 or bf16");
-  return t == at::kFloat
-             ? mine_bn_reduce_grid_f32(M, (int)C, (int)max_blocks)
-             : mine_bn_reduce_grid_bf16(M, (int)C, (int)max_blocks);
+  TORCH_CHECK(t == at::kFloat || is_16bit(t),
+              "bn: dtype must be f32, bf16 or fp16");
+  if (t == at::kFloat)
+    return mine_bn_reduce_grid_f32(M, (int)C, (int)max_blocks);
+  return t == at::kHalf ? mine_bn_reduce_grid_f16(M, (int)C, (int)max_blocks)
+                        : mine_bn_reduce_grid_bf16(M, (int)C, (int)max_blocks);
 }
 
 // deterministic stats pass over x: returns the workspace and its grid.x
@@ -632,8 +711,9 @@ std::vector<at::Tensor> bn_stats(at::Tensor x, int64_t M, int64_t C,
 }
 
 // SplitConvBlock join fused into the stats pass (see bn_kernels.hip):
-// y_dec (B*S,HW,C), y_base (B,HW,C), bias (B*S,C), all flat bf16 NHWC.
-// Returns x = bf16(bf16(y_base + bias) + y_dec) and its (sum, sumsq).
+// y_dec (B*S,HW,C), y_base (B,HW,C), bias (B*S,C), flat NHWC, all of one
+// 16-bit type T. Returns x = T(T(y_base + bias) + y_dec) and its
+// (sum, sumsq).
 std::vector<at::Tensor> bn_join_stats(at::Tensor y_dec, at::Tensor y_base,
                                       at::Tensor bias, int64_t B, int64_t S,
                                       int64_t HW, int64_t C,
@@ -641,10 +721,12 @@ std::vector<at::Tensor> bn_join_stats(at::Tensor y_dec, at::Tensor y_base,
                                       bool deterministic) {
   TORCH_CHECK(y_dec.is_cuda() && y_dec.is_contiguous() &&
               y_base.is_contiguous() && bias.is_contiguous());
-  TORCH_CHECK(y_dec.scalar_type() == at::kBFloat16 &&
-              y_base.scalar_type() == at::kBFloat16 &&
-              bias.scalar_type() == at::kBFloat16,
-              "bn_join_stats: bf16 only");
+  const at::ScalarType jt = y_dec.scalar_type();
+  TORCH_CHECK(is_16bit(jt) && y_base.scalar_type() == jt &&
+              bias.scalar_type() == jt,
+              "bn_join_stats: operands must all be bf16 or all fp16");
+  const auto join = jt == at::kHalf ? mine_bn_join_stats_f16
+                                    : mine_bn_join_stats_bf16;
   TORCH_CHECK(C % 8 == 0 && B > 0 && S > 0 && HW > 0 &&
               HW < (int64_t(1) << 31));
   TORCH_CHECK(y_dec.numel() == B * S * HW * C &&
@@ -654,23 +736,21 @@ std::vector<at::Tensor> bn_join_stats(at::Tensor y_dec, at::Tensor y_base,
   if (deterministic) {
     // the finish launch takes the place of the zero fill
     const int64_t M = B * S * HW;
-    const int G = bn_reduce_grid(at::kBFloat16, M, C, max_blocks);
+    const int G = bn_reduce_grid(jt, M, C, max_blocks);
     auto ws = at::empty({G, 2, C}, fopt);
     auto sums = at::empty({2 * C}, fopt);
-    mine_bn_join_stats_bf16(y_dec.data_ptr(), y_base.data_ptr(),
-                            bias.data_ptr(), x.data_ptr(),
-                            ws.data_ptr<float>(), M, (int)HW, (int)S, (int)C,
-                            (int)max_blocks, 1, stream());
+    join(y_dec.data_ptr(), y_base.data_ptr(), bias.data_ptr(), x.data_ptr(),
+         ws.data_ptr<float>(), M, (int)HW, (int)S, (int)C, (int)max_blocks, 1,
+         stream());
     mine_bn_det_finish(ws.data_ptr<float>(), G, (int)C,
                        sums.data_ptr<float>(), nullptr, nullptr, nullptr,
                        nullptr, M, 0.0f, 0.0f, stream());
     return {x, sums};
   }
   auto sums = at::zeros({2 * C}, fopt);
-  mine_bn_join_stats_bf16(y_dec.data_ptr(), y_base.data_ptr(),
-                          bias.data_ptr(), x.data_ptr(),
-                          sums.data_ptr<float>(), B * S * HW, (int)HW, (int)S,
-                          (int)C, (int)max_blocks, 0, stream());
+  join(y_dec.data_ptr(), y_base.data_ptr(), bias.data_ptr(), x.data_ptr(),
+       sums.data_ptr<float>(), B * S * HW, (int)HW, (int)S, (int)C,
+       (int)max_blocks, 0, stream());
   return {x, sums};
 }
 
@@ -826,9 +906,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ssim_bwd", &ssim_bwd);
   mod.def("eav2_fwd", &eav2_fwd, "fused edge-aware smoothness v2 fwd");
   mod.def("eav2_bwd", &eav2_bwd, "fused edge-aware smoothness v2 bwd");
-  mod.def("pack_gather", &pack_gather,
-          "one-launch fragment pack through a device LUT");
   namespace py = pybind11;
+  mod.def("pack_gather", &pack_gather,
+          "one-launch fragment pack through a device LUT", py::arg("w"),
+          py::arg("lut"), py::arg("dtype") = py::none());
   mod.def("conv_igemm_fwd", &conv_igemm_fwd,
           "general igemm conv fwd / data-grad (coordinate-remapped)",
           py::arg("x_flat"), py::arg("wp"), py::arg("bias"), py::arg("M"),
@@ -895,7 +976,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("pad_mode"), py::arg("src_h"), py::arg("src_w"),
           py::arg("off"), py::arg("c_mem") = 0);
   mod.def("conv3x3_pack", &conv3x3_pack,
-          "gather a conv weight into MFMA fragment order (bf16)");
+          "gather a conv weight into MFMA fragment order (bf16 or fp16)",
+          py::arg("w_flat"), py::arg("lut"), py::arg("dtype") = py::none());
   mod.def("conv3x3_wrw", &conv3x3_wrw,
           "reflect-pad 3x3 conv weight gradient, fp32 (K, C, 3, 3)",
           py::arg("x_flat"), py::arg("gy_flat"), py::arg("N"), py::arg("H"),

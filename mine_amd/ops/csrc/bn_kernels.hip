@@ -1,6 +1,6 @@
 // Fused training-mode BatchNorm + activation, CDNA4 (gfx950).
 //
-// bf16 (or fp32) activations in channels_last (logical (N,H,W,C), C
+// bf16, fp16 (or fp32) activations in channels_last (logical (N,H,W,C), C
 // stride 1), fp32 statistics/parameters — the numerically standard
 // mixed-precision BN. Replaces the eager chain
 //   cast-to-f32 -> MIOpen BN (2-3 kernels) -> cast-to-bf16 -> activation
@@ -40,6 +40,10 @@ enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_LRELU = 2, ACT_ELU = 3,
 template <typename T> struct Vec;
 template <> struct Vec<float> { using t = float; };
 template <> struct Vec<__hip_bfloat16> { using t = __hip_bfloat16; };
+// fp16 is the compiler's native half: same bits as __half / at::Half, and
+// its float conversions (RNE, overflow to inf) survive
+// __HIP_NO_HALF_CONVERSIONS__
+template <> struct Vec<_Float16> { using t = _Float16; };
 
 __device__ __forceinline__ float act_fwd(int act, float z) {
   switch (act) {
@@ -721,25 +725,23 @@ bn_act_bwd_dx_vec_kernel(const T* __restrict__ x, const T* __restrict__ res,
 }
 
 // ---------------------------------------------------------------------------
-// SplitConvBlock join fused into the statistics pass (bf16):
-//   x[bs,p,:] = bf16(bf16(y_base[b,p,:] + bias[bs,:]) + y_dec[bs,p,:])
+// SplitConvBlock join fused into the statistics pass (T = bf16 or fp16):
+//   x[bs,p,:] = T(T(y_base[b,p,:] + bias[bs,:]) + y_dec[bs,p,:])
 // with bs = b*S + s over rows m = bs*HW + p, plus the per-channel
 // (sum, sumsq) of the ROUNDED x — what bn_stats_vec_kernel would read
-// back. The two explicit roundings reproduce the eager bf16 add chain
+// back. The two explicit roundings reproduce the eager 16-bit add chain
 // bit for bit. Same lane map and LDS-then-global-atomic reduction as
 // bn_stats_vec_kernel; (p, bs, b) advance incrementally with the fixed
 // row stride, so the loop has no division.
 // ---------------------------------------------------------------------------
 
-template <int V, bool DET>
+template <typename T, int V, bool DET>
 __global__ void __launch_bounds__(kBlock)
-bn_join_stats_vec_kernel(const __hip_bfloat16* __restrict__ y_dec,
-                         const __hip_bfloat16* __restrict__ y_base,
-                         const __hip_bfloat16* __restrict__ bias,
-                         __hip_bfloat16* __restrict__ x,
+bn_join_stats_vec_kernel(const T* __restrict__ y_dec,
+                         const T* __restrict__ y_base,
+                         const T* __restrict__ bias, T* __restrict__ x,
                          float* __restrict__ sums,  // (2,C)
                          int64_t M, int HW, int S, int C, int cgv) {
-  using T = __hip_bfloat16;
   using Vec = BnVec<T, V>;
   const int Cv = C / V;
   const int c0v = blockIdx.y * cgv;
@@ -1034,28 +1036,36 @@ void launch_bn_act_bwd_dx(const void* x, const void* res, const void* gy,
 
 EXPORT_BN(f32, float)
 EXPORT_BN(bf16, __hip_bfloat16)
+EXPORT_BN(f16, _Float16)
 
-// x = bf16(bf16(y_base + bias) + y_dec) and its (sum, sumsq); C % 8 == 0
-extern "C" void mine_bn_join_stats_bf16(const void* y_dec, const void* y_base,
-                                        const void* bias, void* x, float* sums,
-                                        int64_t M, int HW, int S, int C,
-                                        int max_blocks, int det,
-                                        hipStream_t s) {
-  constexpr int V = 8;
-  const int Cv = C / V;
-  const int cgv = chan_group_v(Cv);
-#define JOIN_LAUNCH(DET)                                                      \
-  hipLaunchKernelGGL((bn_join_stats_vec_kernel<V, DET>),                      \
-                     grid_reduce_v(M, Cv, cgv, max_blocks), dim3(kBlock), 0,  \
-                     s, reinterpret_cast<const __hip_bfloat16*>(y_dec),       \
-                     reinterpret_cast<const __hip_bfloat16*>(y_base),         \
-                     reinterpret_cast<const __hip_bfloat16*>(bias),           \
-                     reinterpret_cast<__hip_bfloat16*>(x), sums, M, HW, S, C, \
-                     cgv)
-  if (det) JOIN_LAUNCH(true);
-  else JOIN_LAUNCH(false);
-#undef JOIN_LAUNCH
-}
+// x = T(T(y_base + bias) + y_dec) and its (sum, sumsq); C % 8 == 0
+#define EXPORT_BN_JOIN(SUF, T)                                                 \
+  extern "C" void mine_bn_join_stats_##SUF(                                    \
+      const void* y_dec, const void* y_base, const void* bias, void* x,        \
+      float* sums, int64_t M, int HW, int S, int C, int max_blocks, int det,   \
+      hipStream_t s) {                                                         \
+    constexpr int V = 8;                                                       \
+    const int Cv = C / V;                                                      \
+    const int cgv = chan_group_v(Cv);                                          \
+    const dim3 grid = grid_reduce_v(M, Cv, cgv, max_blocks);                   \
+    if (det)                                                                   \
+      hipLaunchKernelGGL((bn_join_stats_vec_kernel<T, V, true>), grid,         \
+                         dim3(kBlock), 0, s,                                   \
+                         reinterpret_cast<const T*>(y_dec),                    \
+                         reinterpret_cast<const T*>(y_base),                   \
+                         reinterpret_cast<const T*>(bias),                     \
+                         reinterpret_cast<T*>(x), sums, M, HW, S, C, cgv);     \
+    else                                                                       \
+      hipLaunchKernelGGL((bn_join_stats_vec_kernel<T, V, false>), grid,        \
+                         dim3(kBlock), 0, s,                                   \
+                         reinterpret_cast<const T*>(y_dec),                    \
+                         reinterpret_cast<const T*>(y_base),                   \
+                         reinterpret_cast<const T*>(bias),                     \
+                         reinterpret_cast<T*>(x), sums, M, HW, S, C, cgv);     \
+  }
+
+EXPORT_BN_JOIN(bf16, __hip_bfloat16)
+EXPORT_BN_JOIN(f16, _Float16)
 
 // deterministic finish over ws[G][2][C]: writes `out` (2,C) if given and
 // finalizes into mean/invstd (+ running stats) if given

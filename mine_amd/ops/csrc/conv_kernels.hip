@@ -1,4 +1,6 @@
-// Fused reflection-pad + 3x3 stride-1 conv, NHWC bf16, MFMA 16x16x32.
+// Fused reflection-pad + 3x3 stride-1 conv, NHWC bf16 or fp16, MFMA
+// 16x16x32. The element type is a template parameter (elem16.h); the
+// fragment maps, LDS image and store pattern are the same for both.
 // (the reference's ConvBlock conv, ref network/monodepth2/layers.py:106-138)
 //
 // The decoder's hot remaining convs are small-channel 3x3 blocks at
@@ -53,9 +55,11 @@
 #include <hip/hip_bf16.h>
 #include <cstdint>
 
+#include "elem16.h"
+
 namespace {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using elem16::Elem16;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int kBlock = 256;
@@ -136,16 +140,19 @@ struct StageIdx {
 // K = 32; with the 48 / 64 accumulators of NK = 3 / 4 the compiler
 // needs 4 / 3 to stay out of scratch (C = 64 is at 3 by its LDS anyway).
 // KVEC: K % 4 == 0, so a lane's 4 channels go out as one 8-byte store.
-template <int PAD, int CV, int NK, bool CIN4, bool KVEC>
+template <typename T, int PAD, int CV, int NK, bool CIN4, bool KVEC>
 __global__ void __launch_bounds__(kBlock, (NK <= 2 ? 6 : NK == 3 ? 4 : 3))
-conv3x3_fwd_kernel(const __hip_bfloat16* __restrict__ x,  // (N,sH,sW,C)
-                   const bf16x8* __restrict__ wp,         // packed frags
+conv3x3_fwd_kernel(const T* __restrict__ x,               // (N,sH,sW,C)
+                   const typename Elem16<T>::frag8* __restrict__ wp,  // frags
                    const float* __restrict__ bias,        // (K) or null
-                   __hip_bfloat16* __restrict__ out,      // (N,H,W,K)
+                   T* __restrict__ out,                   // (N,H,W,K)
                    int H, int W, int K, int k0,
                    int sH, int sW, int off) {
+  using E = Elem16<T>;
+  using raw = typename E::raw;
+  using frag8 = typename E::frag8;
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
-  bf16x8* s_in = reinterpret_cast<bf16x8*>(s_raw);
+  frag8* s_in = reinterpret_cast<frag8*>(s_raw);
   constexpr int CPIX = CIN4 ? 4 : CV * 8;    // channels per pixel in memory
   constexpr int NSEG = 9 * CV;               // segments of 8 k
   constexpr int NCH = (NSEG + 3) / 4;        // 32-wide K chunks
@@ -160,29 +167,29 @@ conv3x3_fwd_kernel(const __hip_bfloat16* __restrict__ x,  // (N,sH,sW,C)
   // vectors per thread: a batch's loads are all issued before its LDS
   // writes, so a thread keeps that many 16-byte loads in flight ----
   {
-    const __hip_bfloat16* x_n = x + (int64_t)n * sH * sW * CPIX;
+    const T* x_n = x + (int64_t)n * sH * sW * CPIX;
     StageIdx<CV> si(tid), sj(tid);
 #pragma unroll
     for (int b0 = 0; b0 < NIT; b0 += STAGE_BATCH) {
-      bf16x8 v[STAGE_BATCH];
+      frag8 v[STAGE_BATCH];
 #pragma unroll
       for (int it = 0; it < STAGE_BATCH; ++it) {
         if (b0 + it >= NIT) break;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[it][e] = (__bf16)0.0f;
+        for (int e = 0; e < 8; ++e) v[it][e] = (raw)0.0f;
         if (si.row < STAGE_H) {
           const int yy = map_coord<PAD>(y0 + si.row - 1, H, sH, off);
           const int xx = map_coord<PAD>(x0 + si.x - 1, W, sW, off);
           if (yy >= 0 && xx >= 0) {
-            const __hip_bfloat16* src =
+            const T* src =
                 x_n + ((int64_t)yy * sW + xx) * CPIX + si.cv * 8;
             if (CIN4) {
-              using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-              const bf16x4 h = *reinterpret_cast<const bf16x4*>(src);
+              using frag4 = typename E::frag4;
+              const frag4 h = *reinterpret_cast<const frag4*>(src);
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[it][e] = h[e];
             } else {
-              v[it] = *reinterpret_cast<const bf16x8*>(src);
+              v[it] = *reinterpret_cast<const frag8*>(src);
             }
           }
         }
@@ -215,8 +222,8 @@ conv3x3_fwd_kernel(const __hip_bfloat16* __restrict__ x,  // (N,sH,sW,C)
 #pragma unroll
     for (int a = 0; a < NK; ++a) acc[r][a] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const bf16x8* s_lane = s_in + px_base + p;
-  const bf16x8* w_lane = wp + lane;
+  const frag8* s_lane = s_in + px_base + p;
+  const frag8* w_lane = wp + lane;
 
 #pragma unroll
   for (int kc = 0; kc < NCH; ++kc) {
@@ -225,22 +232,21 @@ conv3x3_fwd_kernel(const __hip_bfloat16* __restrict__ x,  // (N,sH,sW,C)
                 : g == 1 ? seg_vec_off(kc * 4 + 1, NSEG)
                 : g == 2 ? seg_vec_off(kc * 4 + 2, NSEG)
                          : seg_vec_off(kc * 4 + 3, NSEG);
-    bf16x8 wf[NK];
+    frag8 wf[NK];
 #pragma unroll
     for (int a = 0; a < NK; ++a) wf[a] = w_lane[(a * NCH + kc) * 64];
 #pragma unroll
     for (int r = 0; r < TILE_H; ++r) {
-      bf16x8 b = s_lane[o + r * ROW_PITCH];
+      frag8 b = s_lane[o + r * ROW_PITCH];
       if (kc * 4 + 3 >= NSEG) {  // the zero-padded tail of the K-dim
         if (kc * 4 + g >= NSEG) {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) b[e] = (__bf16)0.0f;
+          for (int e = 0; e < 8; ++e) b[e] = (raw)0.0f;
         }
       }
 #pragma unroll
       for (int a = 0; a < NK; ++a)
-        acc[r][a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[a], b,
-                                                            acc[r][a], 0, 0, 0);
+        acc[r][a] = E::mfma(wf[a], b, acc[r][a]);
     }
   }
 
@@ -261,17 +267,14 @@ conv3x3_fwd_kernel(const __hip_bfloat16* __restrict__ x,  // (N,sH,sW,C)
     for (int r = 0; r < TILE_H; ++r) {
       const int y = y0 + r;
       if (y >= H) break;
-      __hip_bfloat16* dst = out + (((int64_t)n * H + y) * W + pix) * K + kout;
-      __hip_bfloat16 h[4];
+      T* dst = out + (((int64_t)n * H + y) * W + pix) * K + kout;
+      T h[4];
 #pragma unroll
-      for (int c = 0; c < 4; ++c)
-        h[c] = (__hip_bfloat16)(acc[r][a][c] + b4[c]);
+      for (int c = 0; c < 4; ++c) h[c] = E::from_float(acc[r][a][c] + b4[c]);
       if (KVEC) {
         uint2 u;
-        u.x = (uint32_t)__bfloat16_as_ushort(h[0]) |
-              ((uint32_t)__bfloat16_as_ushort(h[1]) << 16);
-        u.y = (uint32_t)__bfloat16_as_ushort(h[2]) |
-              ((uint32_t)__bfloat16_as_ushort(h[3]) << 16);
+        u.x = E::bits(h[0]) | (E::bits(h[1]) << 16);
+        u.y = E::bits(h[2]) | (E::bits(h[3]) << 16);
         *reinterpret_cast<uint2*>(dst) = u;
       } else {
 #pragma unroll
@@ -282,54 +285,53 @@ conv3x3_fwd_kernel(const __hip_bfloat16* __restrict__ x,  // (N,sH,sW,C)
   }
 }
 
-template <int PAD, int CV, int NK, bool CIN4>
+template <typename T, int PAD, int CV, int NK, bool CIN4>
 void launch(const void* x, const void* wp, const float* bias, void* out,
             int N, int H, int W, int K, int k0, int sH, int sW, int off,
             hipStream_t stream) {
   constexpr int NCH = (9 * CV + 3) / 4;
   const dim3 grid((W + TILE_W - 1) / TILE_W, (H + TILE_H - 1) / TILE_H, N);
-  const size_t lds = (size_t)CV * CB_PITCH * sizeof(bf16x8);
+  using frag8 = typename Elem16<T>::frag8;
+  const size_t lds = (size_t)CV * CB_PITCH * sizeof(frag8);
   // weights of output-channel tile k0/16 onwards
-  const bf16x8* wk =
-      reinterpret_cast<const bf16x8*>(wp) + (size_t)(k0 / 16) * NCH * 64;
+  const frag8* wk =
+      reinterpret_cast<const frag8*>(wp) + (size_t)(k0 / 16) * NCH * 64;
   if (K % 4 == 0)
-    hipLaunchKernelGGL((conv3x3_fwd_kernel<PAD, CV, NK, CIN4, true>), grid,
+    hipLaunchKernelGGL((conv3x3_fwd_kernel<T, PAD, CV, NK, CIN4, true>), grid,
                        dim3(kBlock), lds, stream,
-                       reinterpret_cast<const __hip_bfloat16*>(x), wk, bias,
-                       reinterpret_cast<__hip_bfloat16*>(out), H, W, K, k0,
-                       sH, sW, off);
+                       reinterpret_cast<const T*>(x), wk, bias,
+                       reinterpret_cast<T*>(out), H, W, K, k0, sH, sW, off);
   else
-    hipLaunchKernelGGL((conv3x3_fwd_kernel<PAD, CV, NK, CIN4, false>), grid,
+    hipLaunchKernelGGL((conv3x3_fwd_kernel<T, PAD, CV, NK, CIN4, false>), grid,
                        dim3(kBlock), lds, stream,
-                       reinterpret_cast<const __hip_bfloat16*>(x), wk, bias,
-                       reinterpret_cast<__hip_bfloat16*>(out), H, W, K, k0,
-                       sH, sW, off);
+                       reinterpret_cast<const T*>(x), wk, bias,
+                       reinterpret_cast<T*>(out), H, W, K, k0, sH, sW, off);
 }
 
-template <int PAD, int CV, bool CIN4>
+template <typename T, int PAD, int CV, bool CIN4>
 void launch_nk(int nk, const void* x, const void* wp, const float* bias,
                void* out, int N, int H, int W, int K, int k0, int sH, int sW,
                int off, hipStream_t s) {
   switch (nk) {
-    case 1: launch<PAD, CV, 1, CIN4>(x, wp, bias, out, N, H, W, K, k0, sH, sW, off, s); break;
-    case 2: launch<PAD, CV, 2, CIN4>(x, wp, bias, out, N, H, W, K, k0, sH, sW, off, s); break;
-    case 3: launch<PAD, CV, 3, CIN4>(x, wp, bias, out, N, H, W, K, k0, sH, sW, off, s); break;
-    default: launch<PAD, CV, 4, CIN4>(x, wp, bias, out, N, H, W, K, k0, sH, sW, off, s); break;
+    case 1: launch<T, PAD, CV, 1, CIN4>(x, wp, bias, out, N, H, W, K, k0, sH, sW, off, s); break;
+    case 2: launch<T, PAD, CV, 2, CIN4>(x, wp, bias, out, N, H, W, K, k0, sH, sW, off, s); break;
+    case 3: launch<T, PAD, CV, 3, CIN4>(x, wp, bias, out, N, H, W, K, k0, sH, sW, off, s); break;
+    default: launch<T, PAD, CV, 4, CIN4>(x, wp, bias, out, N, H, W, K, k0, sH, sW, off, s); break;
   }
 }
 
-template <int PAD>
+template <typename T, int PAD>
 bool launch_cv(int cv, bool cin4, int nk, const void* x, const void* wp,
                const float* bias, void* out, int N, int H, int W, int K,
                int k0, int sH, int sW, int off, hipStream_t s) {
   if (cin4) {
     if (PAD != PAD_ZERO || cv != 1) return false;
-    launch_nk<PAD_ZERO, 1, true>(nk, x, wp, bias, out, N, H, W, K, k0, sH, sW, off, s);
+    launch_nk<T, PAD_ZERO, 1, true>(nk, x, wp, bias, out, N, H, W, K, k0, sH, sW, off, s);
     return true;
   }
   switch (cv) {
 #define MINE_CONV_CV(V)                                                       \
-    case V: launch_nk<PAD, V, false>(nk, x, wp, bias, out, N, H, W, K, k0,   \
+    case V: launch_nk<T, PAD, V, false>(nk, x, wp, bias, out, N, H, W, K, k0,\
                                      sH, sW, off, s); return true;
     MINE_CONV_CV(1) MINE_CONV_CV(2) MINE_CONV_CV(3) MINE_CONV_CV(4)
     MINE_CONV_CV(5) MINE_CONV_CV(6) MINE_CONV_CV(7) MINE_CONV_CV(8)
@@ -338,61 +340,88 @@ bool launch_cv(int cv, bool cin4, int nk, const void* x, const void* wp,
   return false;
 }
 
-}  // namespace
-
-// C = logical input channels (multiple of 8, <= 64); c_mem = channels
-// per pixel in memory: C, or 4 with C == 8 in zero-embed mode. Output
-// channels beyond 64 run as further launches over the same input.
-// Returns 0, or -1 when no kernel is instantiated for the shape.
-extern "C" int mine_conv3x3_fwd(const void* x, const void* wp,
-                                const float* bias, void* out, int N, int H,
-                                int W, int C, int c_mem, int K, int pad_mode,
-                                int src_h, int src_w, int off,
-                                hipStream_t stream) {
-  if (C % 8 || C < 8 || C > 64 || K < 1) return -1;
+template <typename T>
+int conv3x3_fwd_t(const void* x, const void* wp, const float* bias, void* out,
+                  int N, int H, int W, int C, int c_mem, int K, int pad_mode,
+                  int src_h, int src_w, int off, hipStream_t stream) {
   const bool cin4 = c_mem != C;
-  if (cin4 && !(c_mem == 4 && C == 8)) return -1;
   for (int k0 = 0; k0 < K; k0 += 64) {
     const int nk = (((K - k0) < 64 ? (K - k0) : 64) + 15) / 16;
     const bool ok =
         pad_mode == PAD_REFLECT
-            ? launch_cv<PAD_REFLECT>(C / 8, cin4, nk, x, wp, bias, out, N, H,
-                                     W, K, k0, src_h, src_w, off, stream)
-            : launch_cv<PAD_ZERO>(C / 8, cin4, nk, x, wp, bias, out, N, H, W,
-                                  K, k0, src_h, src_w, off, stream);
+            ? launch_cv<T, PAD_REFLECT>(C / 8, cin4, nk, x, wp, bias, out, N,
+                                        H, W, K, k0, src_h, src_w, off, stream)
+            : launch_cv<T, PAD_ZERO>(C / 8, cin4, nk, x, wp, bias, out, N, H,
+                                     W, K, k0, src_h, src_w, off, stream);
     if (!ok) return -1;
   }
   return 0;
 }
 
+}  // namespace
+
+// C = logical input channels (multiple of 8, <= 64); c_mem = channels
+// per pixel in memory: C, or 4 with C == 8 in zero-embed mode. Output
+// channels beyond 64 run as further launches over the same input.
+// x, wp and out share one element type: bf16, or fp16 with is_f16.
+// Returns 0, or -1 when no kernel is instantiated for the shape.
+extern "C" int mine_conv3x3_fwd(const void* x, const void* wp,
+                                const float* bias, void* out, int N, int H,
+                                int W, int C, int c_mem, int K, int pad_mode,
+                                int src_h, int src_w, int off, int is_f16,
+                                hipStream_t stream) {
+  if (C % 8 || C < 8 || C > 64 || K < 1) return -1;
+  if (c_mem != C && !(c_mem == 4 && C == 8)) return -1;
+  return is_f16 ? conv3x3_fwd_t<_Float16>(x, wp, bias, out, N, H, W, C, c_mem,
+                                          K, pad_mode, src_h, src_w, off,
+                                          stream)
+                : conv3x3_fwd_t<__hip_bfloat16>(x, wp, bias, out, N, H, W, C,
+                                                c_mem, K, pad_mode, src_h,
+                                                src_w, off, stream);
+}
+
 // Gather a (K,C,3,3) weight into MFMA fragment order in one launch:
-// out[i] = bf16(w[lut[i]]), or 0 where lut[i] is the one-past-the-end
-// pad slot. fp32 -> bf16 rounds to nearest even, as torch's cast does.
+// out[i] = TOUT(w[lut[i]]), or 0 where lut[i] is the one-past-the-end
+// pad slot. fp32 -> bf16 / fp16 rounds to nearest even, as torch's cast
+// does.
 namespace {
-template <typename T>
+template <typename TIN, typename TOUT>
 __global__ void __launch_bounds__(kBlock)
-conv3x3_pack_kernel(const T* __restrict__ w, const int64_t* __restrict__ lut,
-                    __hip_bfloat16* __restrict__ out, int64_t n_out,
-                    int64_t n_w) {
+conv3x3_pack_kernel(const TIN* __restrict__ w, const int64_t* __restrict__ lut,
+                    TOUT* __restrict__ out, int64_t n_out, int64_t n_w) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n_out) return;
   const int64_t j = lut[i];
-  out[i] = (j >= 0 && j < n_w) ? (__hip_bfloat16)(float)w[j]
-                               : (__hip_bfloat16)0.0f;
+  out[i] = (j >= 0 && j < n_w) ? (TOUT)(float)w[j] : (TOUT)0.0f;
+}
+
+template <typename TOUT>
+void pack_t(const void* w, int w_kind, const int64_t* lut, void* out,
+            int64_t n_out, int64_t n_w, hipStream_t stream) {
+  const dim3 grid((unsigned)((n_out + kBlock - 1) / kBlock));
+  TOUT* o = reinterpret_cast<TOUT*>(out);
+  if (w_kind == 1)
+    hipLaunchKernelGGL((conv3x3_pack_kernel<__hip_bfloat16, TOUT>), grid,
+                       dim3(kBlock), 0, stream,
+                       reinterpret_cast<const __hip_bfloat16*>(w), lut, o,
+                       n_out, n_w);
+  else if (w_kind == 2)
+    hipLaunchKernelGGL((conv3x3_pack_kernel<_Float16, TOUT>), grid,
+                       dim3(kBlock), 0, stream,
+                       reinterpret_cast<const _Float16*>(w), lut, o, n_out,
+                       n_w);
+  else
+    hipLaunchKernelGGL((conv3x3_pack_kernel<float, TOUT>), grid, dim3(kBlock),
+                       0, stream, reinterpret_cast<const float*>(w), lut, o,
+                       n_out, n_w);
 }
 }  // namespace
 
-extern "C" void mine_conv3x3_pack(const void* w, int is_bf16,
-                                  const int64_t* lut, void* out,
+// w_kind: 0 fp32, 1 bf16, 2 fp16; the output is bf16, or fp16 with out_f16
+extern "C" void mine_conv3x3_pack(const void* w, int w_kind,
+                                  const int64_t* lut, void* out, int out_f16,
                                   int64_t n_out, int64_t n_w,
                                   hipStream_t stream) {
-  const dim3 grid((unsigned)((n_out + kBlock - 1) / kBlock));
-  if (is_bf16)
-    hipLaunchKernelGGL(conv3x3_pack_kernel<__hip_bfloat16>, grid, dim3(kBlock),
-                       0, stream, reinterpret_cast<const __hip_bfloat16*>(w),
-                       lut, reinterpret_cast<__hip_bfloat16*>(out), n_out, n_w);
-  else
-    hipLaunchKernelGGL(conv3x3_pack_kernel<float>, grid, dim3(kBlock), 0,
-                       stream, reinterpret_cast<const float*>(w), lut,
-                       reinterpret_cast<__hip_bfloat16*>(out), n_out, n_w);
+  if (out_f16) pack_t<_Float16>(w, w_kind, lut, out, n_out, n_w, stream);
+  else pack_t<__hip_bfloat16>(w, w_kind, lut, out, n_out, n_w, stream);
 }

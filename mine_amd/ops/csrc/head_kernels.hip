@@ -105,3 +105,4 @@ inline int grid_for(int64_t n) {
 
 EXPORT_HEAD(f32, float)
 EXPORT_HEAD(bf16, __hip_bfloat16)
+EXPORT_HEAD(f16, _Float16)

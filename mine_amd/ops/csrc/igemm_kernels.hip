@@ -1,7 +1,8 @@
 // General MFMA implicit-GEMM convolution family for the encoder / neck /
 // base-conv shapes (ResNet-50 stack: 1x1 s1/s2, 3x3 s1/s2, 7x7 s2 stem;
 // the decoder's reflect-padded batch-B base convs) — forward, data-grad
-// and weight-grad, NHWC bf16, fp32 accumulate.
+// and weight-grad, NHWC bf16 or fp16 (template parameter T, elem16.h),
+// fp32 accumulate.
 //
 // Design (MI355X): every one of these tensors is small (batch 4,
 // <=13 MB — L2/L3 resident) and the library path was LAUNCH/LATENCY
@@ -32,9 +33,11 @@
 #include <hip/hip_bf16.h>
 #include <cstdint>
 
+#include "elem16.h"
+
 namespace {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using elem16::Elem16;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using s16x4 = __attribute__((ext_vector_type(4))) short;
 using s16x8 = __attribute__((ext_vector_type(8))) short;
@@ -80,16 +83,18 @@ __device__ __forceinline__ int src_coord(int p, int r, int SA, int SB,
 // stores into ws_out[z][M][K] (no zero fill needed: every slice writes
 // every valid element of its tile) and igemm_epilogue_det_kernel adds the
 // slices in ascending z. Same splitz, same kc_begin/kc_end.
-template <int Sdim, int RS, int PAD, bool SPLIT, bool DET>
+template <typename T, int Sdim, int RS, int PAD, bool SPLIT, bool DET>
 __global__ void __launch_bounds__(kBlock)
-conv_igemm_fwd_kernel(const __hip_bfloat16* __restrict__ x,  // (N,Hs,Ws,C)
-                      const __hip_bfloat16* __restrict__ wp, // packed frags
+conv_igemm_fwd_kernel(const T* __restrict__ x,               // (N,Hs,Ws,C)
+                      const T* __restrict__ wp,              // packed frags
                       const float* __restrict__ bias,        // (K) or null
-                      __hip_bfloat16* __restrict__ out,      // (M,K) flat
+                      T* __restrict__ out,                   // (M,K) flat
                       float* __restrict__ ws_out,            // (M,K) fp32
                       int64_t M, int P, int Q, int K,
                       int Hs, int Ws, int C,
                       int SA, int SB, int SD, int SE) {
+  using E = Elem16<T>;
+  using frag8 = typename E::frag8;
   const int64_t m_lane = (int64_t)blockIdx.x * 64 +
                          (threadIdx.x >> 6) * 16 + (threadIdx.x & 15);
   const int lane = threadIdx.x & 63;
@@ -124,7 +129,7 @@ conv_igemm_fwd_kernel(const __hip_bfloat16* __restrict__ x,  // (N,Hs,Ws,C)
 
   for (int kc = kc_begin; kc < kc_end; ++kc) {
     const int seg = kc * 4 + (lane >> 4);
-    bf16x8 afrag;
+    frag8 afrag;
     bool loaded = false;
     if (m_ok && seg < nseg) {
       const int tap = seg / Cv;
@@ -134,23 +139,22 @@ conv_igemm_fwd_kernel(const __hip_bfloat16* __restrict__ x,  // (N,Hs,Ws,C)
       const int ys = src_coord<PAD>(p, r, SA, SB, SD, SE, Hs);
       const int xs = src_coord<PAD>(q, s, SA, SB, SD, SE, Ws);
       if (ys >= 0 && xs >= 0) {
-        afrag = *reinterpret_cast<const bf16x8*>(
+        afrag = *reinterpret_cast<const frag8*>(
             x + (((int64_t)n * Hs + ys) * Ws + xs) * C + coct * 8);
         loaded = true;
       }
     }
     if (!loaded) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) afrag[e] = (__bf16)0.0f;
+      for (int e = 0; e < 8; ++e) afrag[e] = (typename E::raw)0.0f;
     }
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       if (a < nk_here) {
-        const bf16x8 bfrag = *reinterpret_cast<const bf16x8*>(
+        const frag8 bfrag = *reinterpret_cast<const frag8*>(
             wp + (((int64_t)(blockIdx.y * 4 + a) * nchunks + kc) * 64 +
                   lane) * 8);
-        acc[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag, bfrag,
-                                                         acc[a], 0, 0, 0);
+        acc[a] = E::mfma(afrag, bfrag, acc[a]);
       }
     }
   }
@@ -174,37 +178,38 @@ conv_igemm_fwd_kernel(const __hip_bfloat16* __restrict__ x,  // (N,Hs,Ws,C)
         } else if (SPLIT) {
           atomicAdd(&ws_out[mm * K + kout], acc[a][rr]);
         } else {
-          out[mm * K + kout] = (__hip_bfloat16)(acc[a][rr] + b);
+          out[mm * K + kout] = (T)(acc[a][rr] + b);
         }
       }
     }
   }
 }
 
+template <typename T>
 __global__ void __launch_bounds__(kBlock)
 igemm_epilogue_kernel(const float* __restrict__ ws,
                       const float* __restrict__ bias,
-                      __hip_bfloat16* __restrict__ out, int64_t total,
-                      int K) {
+                      T* __restrict__ out, int64_t total, int K) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= total) return;
   const float b = bias ? bias[(int)(i % K)] : 0.0f;
-  out[i] = (__hip_bfloat16)(ws[i] + b);
+  out[i] = (T)(ws[i] + b);
 }
 
 // deterministic split-K epilogue over ws[splitz][M][K]: adds the slices
 // in ascending z, then the bias, then casts
+template <typename T>
 __global__ void __launch_bounds__(kBlock)
 igemm_epilogue_det_kernel(const float* __restrict__ ws,
                           const float* __restrict__ bias,
-                          __hip_bfloat16* __restrict__ out, int64_t total,
-                          int K, int splitz) {
+                          T* __restrict__ out, int64_t total, int K,
+                          int splitz) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= total) return;
   float acc = ws[i];
   for (int z = 1; z < splitz; ++z) acc += ws[(int64_t)z * total + i];
   const float b = bias ? bias[(int)(i % K)] : 0.0f;
-  out[i] = (__hip_bfloat16)(acc + b);
+  out[i] = (T)(acc + b);
 }
 
 // ---------------------------------------------------------------------------
@@ -220,7 +225,8 @@ __device__ __forceinline__ int img_elem32(int col, int j) {
   return bi * 64 + (j & 3) * 16 + col;
 }
 
-__device__ __forceinline__ bf16x8 frag32(const __hip_bfloat16* base) {
+template <typename T>
+__device__ __forceinline__ typename Elem16<T>::frag8 frag32(const T* base) {
   const int l = threadIdx.x & 63;
   const lds_short* pp = (const lds_short*)(base) +
                         (l & 15) * 4 + (l >> 4) * 64;
@@ -228,24 +234,24 @@ __device__ __forceinline__ bf16x8 frag32(const __hip_bfloat16* base) {
   s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
       (lds_s16x4*)(pp + 32 * 8));
   s16x8 s = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, s);
+  return __builtin_bit_cast(typename Elem16<T>::frag8, s);
 }
 
 // DET: `dw` is the workspace ws[n_slabs][K][C][RS]; each block stores its
 // 16x16 tile of slab `slab` with plain stores (every valid element of
 // every slab is written, so no zero fill), and igemm_wrw_finish_kernel
 // adds the slabs in ascending order. Same slab count and m_begin/m_end.
-template <int Sdim, int PAD, bool DET>
+template <typename T, int Sdim, int PAD, bool DET>
 __global__ void __launch_bounds__(64)
-conv_igemm_wrw_kernel(const __hip_bfloat16* __restrict__ x,   // (N,Hs,Ws,C)
-                      const __hip_bfloat16* __restrict__ gy,  // (M,K) flat
+conv_igemm_wrw_kernel(const T* __restrict__ x,                // (N,Hs,Ws,C)
+                      const T* __restrict__ gy,               // (M,K) flat
                       float* __restrict__ dw,                 // (K,C,R,S)
                       int64_t M, int P, int Q, int K,
                       int Hs, int Ws, int C, int RS,
                       int SA, int SB, int SD, int SE, int n_slabs) {
   // one wave per block: gy image + x image, 1 KiB each
-  __shared__ __attribute__((aligned(16))) __hip_bfloat16 s_gy[2][512];
-  __shared__ __attribute__((aligned(16))) __hip_bfloat16 s_x[2][512];
+  __shared__ __attribute__((aligned(16))) T s_gy[2][512];
+  __shared__ __attribute__((aligned(16))) T s_x[2][512];
 
   const int k0 = blockIdx.y * 16;
   const int tap = blockIdx.z / ((C + 15) / 16);
@@ -309,8 +315,7 @@ conv_igemm_wrw_kernel(const __hip_bfloat16* __restrict__ x,   // (N,Hs,Ws,C)
     }
     // single wave: ds ops are in-order per wave; wait for the writes
     __builtin_amdgcn_s_waitcnt(0);  // lgkmcnt(0) | vmcnt(0)
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-        frag32(s_gy[buf]), frag32(s_x[buf]), acc, 0, 0, 0);
+    acc = Elem16<T>::mfma(frag32<T>(s_gy[buf]), frag32<T>(s_x[buf]), acc);
   }
 
   // flush: row = k (lane>>4)*4+rr, col = c (lane&15)
@@ -351,31 +356,43 @@ igemm_wrw_finish_kernel(const float* __restrict__ ws, float* __restrict__ dw,
 // ONE kernel launch regardless of the weight's logical layout.
 // ---------------------------------------------------------------------------
 
-template <typename TIN>
+template <typename TIN, typename TOUT>
 __global__ void __launch_bounds__(kBlock)
 pack_gather_kernel(const TIN* __restrict__ w, const int* __restrict__ lut,
-                   __hip_bfloat16* __restrict__ out, int64_t n) {
+                   TOUT* __restrict__ out, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   const int idx = lut[i];
-  out[i] = (idx >= 0) ? (__hip_bfloat16)(float)w[idx] : (__hip_bfloat16)0.0f;
+  out[i] = (idx >= 0) ? (TOUT)(float)w[idx] : (TOUT)0.0f;
+}
+
+template <typename TOUT>
+void pack_gather_t(const void* w, const int* lut, void* out, int64_t n,
+                   int w_kind, hipStream_t stream) {
+  const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+  TOUT* o = reinterpret_cast<TOUT*>(out);
+  if (w_kind == 1)
+    hipLaunchKernelGGL((pack_gather_kernel<__hip_bfloat16, TOUT>), grid,
+                       dim3(kBlock), 0, stream,
+                       reinterpret_cast<const __hip_bfloat16*>(w), lut, o, n);
+  else if (w_kind == 2)
+    hipLaunchKernelGGL((pack_gather_kernel<_Float16, TOUT>), grid,
+                       dim3(kBlock), 0, stream,
+                       reinterpret_cast<const _Float16*>(w), lut, o, n);
+  else
+    hipLaunchKernelGGL((pack_gather_kernel<float, TOUT>), grid, dim3(kBlock),
+                       0, stream, reinterpret_cast<const float*>(w), lut, o,
+                       n);
 }
 
 }  // namespace
 
+// w_kind: 0 fp32, 1 bf16, 2 fp16; the output is bf16, or fp16 with out_f16
 extern "C" void mine_pack_gather(const void* w, const int* lut, void* out,
-                                 int64_t n, int is_fp32,
+                                 int64_t n, int w_kind, int out_f16,
                                  hipStream_t stream) {
-  const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-  if (is_fp32)
-    hipLaunchKernelGGL(pack_gather_kernel<float>, grid, dim3(kBlock), 0,
-                       stream, reinterpret_cast<const float*>(w), lut,
-                       reinterpret_cast<__hip_bfloat16*>(out), n);
-  else
-    hipLaunchKernelGGL(pack_gather_kernel<__hip_bfloat16>, grid,
-                       dim3(kBlock), 0, stream,
-                       reinterpret_cast<const __hip_bfloat16*>(w), lut,
-                       reinterpret_cast<__hip_bfloat16*>(out), n);
+  if (out_f16) pack_gather_t<_Float16>(w, lut, out, n, w_kind, stream);
+  else pack_gather_t<__hip_bfloat16>(w, lut, out, n, w_kind, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -393,10 +410,10 @@ extern "C" void mine_pack_gather(const void* w, const int* lut, void* out,
     KERNEL_CALL;                                                          \
   }
 
-// splitz > 1 requires ws: pre-zeroed fp32 (M,K), or with det an
-// unfilled fp32 (splitz,M,K); the epilogue launch adds the bias (det: and
-// the slices, in ascending order) and casts into out.
-extern "C" void mine_conv_igemm_fwd(
+namespace {
+
+template <typename T>
+void igemm_fwd_t(
     const void* x, const void* wp, const float* bias, void* out, float* ws,
     int64_t M, int P, int Q, int K, int Hs, int Ws, int C,
     int R, int S, int SA, int SB, int SD, int SE, int pad_mode, int splitz,
@@ -404,11 +421,12 @@ extern "C" void mine_conv_igemm_fwd(
   const dim3 grid((unsigned)((M + 63) / 64), (unsigned)((K + 63) / 64),
                   (unsigned)(splitz > 1 ? splitz : 1));
 #define CALL_FWD(SPLIT, DET)                                             \
-  hipLaunchKernelGGL((conv_igemm_fwd_kernel<Sdim, RS, PAD, SPLIT, DET>), \
-                     grid, dim3(kBlock), 0, stream,                      \
-                     reinterpret_cast<const __hip_bfloat16*>(x),         \
-                     reinterpret_cast<const __hip_bfloat16*>(wp), bias,  \
-                     reinterpret_cast<__hip_bfloat16*>(out), ws,         \
+  hipLaunchKernelGGL(                                                    \
+      (conv_igemm_fwd_kernel<T, Sdim, RS, PAD, SPLIT, DET>), grid,       \
+                     dim3(kBlock), 0, stream,                            \
+                     reinterpret_cast<const T*>(x),                      \
+                     reinterpret_cast<const T*>(wp), bias,               \
+                     reinterpret_cast<T*>(out), ws,                      \
                      M, P, Q, K, Hs, Ws, C, SA, SB, SD, SE)
 #define CALL_FWD_EITHER                                                  \
   do {                                                                   \
@@ -427,17 +445,36 @@ extern "C" void mine_conv_igemm_fwd(
     const int64_t total = M * K;
     const dim3 egrid((unsigned)((total + kBlock - 1) / kBlock));
     if (det)
-      hipLaunchKernelGGL(igemm_epilogue_det_kernel, egrid, dim3(kBlock), 0,
-                         stream, ws, bias,
-                         reinterpret_cast<__hip_bfloat16*>(out), total, K,
-                         splitz);
+      hipLaunchKernelGGL(igemm_epilogue_det_kernel<T>, egrid, dim3(kBlock),
+                         0, stream, ws, bias, reinterpret_cast<T*>(out),
+                         total, K, splitz);
     else
-      hipLaunchKernelGGL(igemm_epilogue_kernel, egrid, dim3(kBlock), 0,
-                         stream, ws, bias,
-                         reinterpret_cast<__hip_bfloat16*>(out), total, K);
+      hipLaunchKernelGGL(igemm_epilogue_kernel<T>, egrid, dim3(kBlock), 0,
+                         stream, ws, bias, reinterpret_cast<T*>(out), total,
+                         K);
   }
 #undef CALL_FWD_EITHER
 #undef CALL_FWD
+}
+
+}  // namespace
+
+// splitz > 1 requires ws: pre-zeroed fp32 (M,K), or with det an
+// unfilled fp32 (splitz,M,K); the epilogue launch adds the bias (det: and
+// the slices, in ascending order) and casts into out. x, wp and out are
+// bf16, or fp16 with is_f16.
+extern "C" void mine_conv_igemm_fwd(
+    const void* x, const void* wp, const float* bias, void* out, float* ws,
+    int64_t M, int P, int Q, int K, int Hs, int Ws, int C,
+    int R, int S, int SA, int SB, int SD, int SE, int pad_mode, int splitz,
+    int det, int is_f16, hipStream_t stream) {
+  if (is_f16)
+    igemm_fwd_t<_Float16>(x, wp, bias, out, ws, M, P, Q, K, Hs, Ws, C, R, S,
+                          SA, SB, SD, SE, pad_mode, splitz, det, stream);
+  else
+    igemm_fwd_t<__hip_bfloat16>(x, wp, bias, out, ws, M, P, Q, K, Hs, Ws, C,
+                                R, S, SA, SB, SD, SE, pad_mode, splitz, det,
+                                stream);
 }
 
 // pixel slabs of the weight gradient (grid.x); the deterministic mode's
@@ -454,10 +491,10 @@ extern "C" int mine_conv_igemm_wrw_slabs(int64_t M, int K, int C, int R,
   return slabs;
 }
 
-// ws_det == nullptr: atomics into the pre-zeroed dw. Otherwise the
-// deterministic pair: tiles into ws_det (slabs,K,C,R,S), unfilled, then
-// the finishing kernel writes dw (unfilled too).
-extern "C" void mine_conv_igemm_wrw(
+namespace {
+
+template <typename T>
+void igemm_wrw_t(
     const void* x, const void* gy, float* dw, float* ws_det,
     int64_t M, int P, int Q, int K, int Hs, int Ws, int C,
     int R, int S, int SA, int SB, int SD, int SE, int pad_mode,
@@ -467,10 +504,10 @@ extern "C" void mine_conv_igemm_wrw(
   const int slabs = mine_conv_igemm_wrw_slabs(M, K, C, R, S);
   const dim3 grid((unsigned)slabs, (unsigned)kc, (unsigned)(cg * R * S));
 #define CALL_WRW_T(DET, DST)                                             \
-  hipLaunchKernelGGL((conv_igemm_wrw_kernel<Sdim, PAD, DET>), grid,      \
+  hipLaunchKernelGGL((conv_igemm_wrw_kernel<T, Sdim, PAD, DET>), grid,   \
                      dim3(64), 0, stream,                                \
-                     reinterpret_cast<const __hip_bfloat16*>(x),         \
-                     reinterpret_cast<const __hip_bfloat16*>(gy), DST,   \
+                     reinterpret_cast<const T*>(x),                      \
+                     reinterpret_cast<const T*>(gy), DST,                \
                      M, P, Q, K, Hs, Ws, C, R * S, SA, SB, SD, SE, slabs)
 #define CALL_WRW                                                         \
   do {                                                                   \
@@ -492,4 +529,23 @@ extern "C" void mine_conv_igemm_wrw(
                        dim3((unsigned)((n + kBlock - 1) / kBlock)),
                        dim3(kBlock), 0, stream, ws_det, dw, n, slabs);
   }
+}
+
+}  // namespace
+
+// ws_det == nullptr: atomics into the pre-zeroed dw. Otherwise the
+// deterministic pair: tiles into ws_det (slabs,K,C,R,S), unfilled, then
+// the finishing kernel writes dw (unfilled too). x and gy are bf16, or
+// fp16 with is_f16.
+extern "C" void mine_conv_igemm_wrw(
+    const void* x, const void* gy, float* dw, float* ws_det,
+    int64_t M, int P, int Q, int K, int Hs, int Ws, int C,
+    int R, int S, int SA, int SB, int SD, int SE, int pad_mode, int is_f16,
+    hipStream_t stream) {
+  if (is_f16)
+    igemm_wrw_t<_Float16>(x, gy, dw, ws_det, M, P, Q, K, Hs, Ws, C, R, S, SA,
+                          SB, SD, SE, pad_mode, stream);
+  else
+    igemm_wrw_t<__hip_bfloat16>(x, gy, dw, ws_det, M, P, Q, K, Hs, Ws, C, R,
+                                S, SA, SB, SD, SE, pad_mode, stream);
 }

@@ -13,7 +13,7 @@
 // Layout: one kernel over a logically contiguous (N, H, W, C) array.
 //   channels_last (B,C,H,W)@NHWC  -> N=B,   C=C (lane-adjacent channels)
 //   contiguous    (B,C,H,W)@NCHW  -> N=B*C, C=1
-// Both dtypes (float, bf16) with fp32 accumulation for the backward.
+// All dtypes (float, bf16, fp16) with fp32 accumulation for the backward.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -152,6 +152,14 @@ void mine_reflect_pad_fwd_bf16(const void* in, void* out, int N, int H,
              reinterpret_cast<__hip_bfloat16*>(out), N, H, W, C, pad);
 }
 
+void mine_reflect_pad_fwd_f16(const void* in, void* out, int N, int H,
+                              int W, int C, int pad, hipStream_t stream) {
+  PAD_LAUNCH(reflect_pad_fwd_kernel, _Float16,
+             (int64_t)N * (H + 2 * pad) * (W + 2 * pad) * C,
+             reinterpret_cast<const _Float16*>(in),
+             reinterpret_cast<_Float16*>(out), N, H, W, C, pad);
+}
+
 void mine_reflect_pad_bwd_f32(const float* gout, float* gin, int N, int H,
                               int W, int C, int pad, hipStream_t stream) {
   PAD_LAUNCH(reflect_pad_bwd_kernel, float, (int64_t)N * H * W * C,
@@ -163,6 +171,13 @@ void mine_reflect_pad_bwd_bf16(const void* gout, void* gin, int N, int H,
   PAD_LAUNCH(reflect_pad_bwd_kernel, __hip_bfloat16, (int64_t)N * H * W * C,
              reinterpret_cast<const __hip_bfloat16*>(gout),
              reinterpret_cast<__hip_bfloat16*>(gin), N, H, W, C, pad);
+}
+
+void mine_reflect_pad_bwd_f16(const void* gout, void* gin, int N, int H,
+                              int W, int C, int pad, hipStream_t stream) {
+  PAD_LAUNCH(reflect_pad_bwd_kernel, _Float16, (int64_t)N * H * W * C,
+             reinterpret_cast<const _Float16*>(gout),
+             reinterpret_cast<_Float16*>(gin), N, H, W, C, pad);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// Nearest x2 upsample, NHWC, bf16/f32 — fwd + bwd.
+// Nearest x2 upsample, NHWC, bf16/fp16/f32 — fwd + bwd.
 //
 // The decoder's five up-stages (ref network/monodepth2/layers.py:198-201,
 // depth_decoder.py:127-133) move ~1.4 GB/step at the flagship config;
@@ -18,7 +18,14 @@ constexpr int kBlock = 256;
 
 template <typename T, int VEC>
 struct VecT;
+
+// the register type behind a 16-bit storage type
+template <typename T> struct Raw16 { using type = T; };
+template <> struct Raw16<__hip_bfloat16> { using type = __bf16; };
 template <> struct VecT<__hip_bfloat16, 8> {
+  using type = __attribute__((ext_vector_type(8))) short;
+};
+template <> struct VecT<_Float16, 8> {
   using type = __attribute__((ext_vector_type(8))) short;
 };
 template <> struct VecT<float, 4> {
@@ -71,12 +78,13 @@ upsample2x_bwd_kernel(const T* __restrict__ gout, T* __restrict__ gin,
 #pragma unroll
   for (int e = 0; e < VEC; ++e) {
     if constexpr (sizeof(T) == 2) {
-      // raw-bit short <-> bf16 via the __bf16 builtin type
-      const float s = (float)__builtin_bit_cast(__bf16, (short)a[e]) +
-                      (float)__builtin_bit_cast(__bf16, (short)b[e]) +
-                      (float)__builtin_bit_cast(__bf16, (short)c[e]) +
-                      (float)__builtin_bit_cast(__bf16, (short)d[e]);
-      o[e] = __builtin_bit_cast(short, (__bf16)s);
+      // raw-bit short <-> bf16 / fp16 via the builtin register type
+      using R = typename Raw16<T>::type;
+      const float s = (float)__builtin_bit_cast(R, (short)a[e]) +
+                      (float)__builtin_bit_cast(R, (short)b[e]) +
+                      (float)__builtin_bit_cast(R, (short)c[e]) +
+                      (float)__builtin_bit_cast(R, (short)d[e]);
+      o[e] = __builtin_bit_cast(short, (R)s);
     } else {
       o[e] = a[e] + b[e] + c[e] + d[e];
     }
@@ -86,50 +94,54 @@ upsample2x_bwd_kernel(const T* __restrict__ gout, T* __restrict__ gin,
 
 }  // namespace
 
+namespace {
+
+template <typename T, int VEC>
+void upsample_fwd_t(const void* in, void* out, int64_t N, int64_t H,
+                    int64_t W, int64_t C, hipStream_t stream) {
+  const int64_t total_v = N * H * W * (C / VEC);
+  const int64_t grid = (total_v + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL((upsample2x_fwd_kernel<T, VEC>), dim3((uint32_t)grid),
+                     dim3(kBlock), 0, stream, reinterpret_cast<const T*>(in),
+                     reinterpret_cast<T*>(out), total_v, (int)W, (int)C);
+}
+
+template <typename T, int VEC>
+void upsample_bwd_t(const void* gout, void* gin, int64_t N, int64_t H,
+                    int64_t W, int64_t C, hipStream_t stream) {
+  const int64_t total_v = N * H * W * (C / VEC);
+  const int64_t grid = (total_v + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL((upsample2x_bwd_kernel<T, VEC>), dim3((uint32_t)grid),
+                     dim3(kBlock), 0, stream,
+                     reinterpret_cast<const T*>(gout),
+                     reinterpret_cast<T*>(gin), total_v, (int)W, (int)C);
+}
+
+}  // namespace
+
 extern "C" {
 
+// kind: 0 fp32 (C % 4 == 0), 1 bf16, 2 fp16 (C % 8 == 0)
 void mine_upsample2x_fwd(const void* in, void* out, int64_t N, int64_t H,
-                         int64_t W, int64_t C, int is_bf16,
+                         int64_t W, int64_t C, int kind,
                          hipStream_t stream) {
-  if (is_bf16) {
-    const int64_t total_v = N * H * W * (C / 8);
-    const int64_t grid = (total_v + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL((upsample2x_fwd_kernel<__hip_bfloat16, 8>),
-                       dim3((uint32_t)grid), dim3(kBlock), 0, stream,
-                       reinterpret_cast<const __hip_bfloat16*>(in),
-                       reinterpret_cast<__hip_bfloat16*>(out),
-                       total_v, (int)W, (int)C);
-  } else {
-    const int64_t total_v = N * H * W * (C / 4);
-    const int64_t grid = (total_v + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL((upsample2x_fwd_kernel<float, 4>),
-                       dim3((uint32_t)grid), dim3(kBlock), 0, stream,
-                       reinterpret_cast<const float*>(in),
-                       reinterpret_cast<float*>(out),
-                       total_v, (int)W, (int)C);
-  }
+  if (kind == 1)
+    upsample_fwd_t<__hip_bfloat16, 8>(in, out, N, H, W, C, stream);
+  else if (kind == 2)
+    upsample_fwd_t<_Float16, 8>(in, out, N, H, W, C, stream);
+  else
+    upsample_fwd_t<float, 4>(in, out, N, H, W, C, stream);
 }
 
 void mine_upsample2x_bwd(const void* gout, void* gin, int64_t N, int64_t H,
-                         int64_t W, int64_t C, int is_bf16,
+                         int64_t W, int64_t C, int kind,
                          hipStream_t stream) {
-  if (is_bf16) {
-    const int64_t total_v = N * H * W * (C / 8);
-    const int64_t grid = (total_v + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL((upsample2x_bwd_kernel<__hip_bfloat16, 8>),
-                       dim3((uint32_t)grid), dim3(kBlock), 0, stream,
-                       reinterpret_cast<const __hip_bfloat16*>(gout),
-                       reinterpret_cast<__hip_bfloat16*>(gin),
-                       total_v, (int)W, (int)C);
-  } else {
-    const int64_t total_v = N * H * W * (C / 4);
-    const int64_t grid = (total_v + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL((upsample2x_bwd_kernel<float, 4>),
-                       dim3((uint32_t)grid), dim3(kBlock), 0, stream,
-                       reinterpret_cast<const float*>(gout),
-                       reinterpret_cast<float*>(gin),
-                       total_v, (int)W, (int)C);
-  }
+  if (kind == 1)
+    upsample_bwd_t<__hip_bfloat16, 8>(gout, gin, N, H, W, C, stream);
+  else if (kind == 2)
+    upsample_bwd_t<_Float16, 8>(gout, gin, N, H, W, C, stream);
+  else
+    upsample_bwd_t<float, 4>(gout, gin, N, H, W, C, stream);
 }
 
 }  // extern "C"

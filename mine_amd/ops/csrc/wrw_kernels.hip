@@ -3,7 +3,9 @@
 //   dW[k, c, dy, dx] = sum_{n,y,x} gy[n,y,x,k] * xpad[n, y+dy, x+dx, c]
 //   db[k]            = sum_{n,y,x} gy[n,y,x,k]
 // as a GEMM with M = K (out-channels), N = 9*C taps, contraction over
-// the pixels, on v_mfma_f32_16x16x32_bf16.
+// the pixels, on v_mfma_f32_16x16x32_bf16 or _f16 (the element type is a
+// template parameter, elem16.h; the kernel moves raw 16-bit words, so only
+// the MFMA and the 1.0 of the bias sum depend on it).
 //
 // v3 design: every tensor is read once and the work is split by output,
 // not by contraction.
@@ -46,9 +48,11 @@
 #include <hip/hip_bf16.h>
 #include <cstdint>
 
+#include "elem16.h"
+
 namespace {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using elem16::Elem16;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using s16x4 = __attribute__((ext_vector_type(4))) short;
 using s16x8 = __attribute__((ext_vector_type(8))) short;
@@ -103,11 +107,12 @@ __device__ __forceinline__ int swz(int j) { return j ^ ((j >> 1) & 4); }
 // 16-lane group passes the address of pixel q, channels 4p..4p+3, and
 // lane i gets channel i of the four pixels. o0 / o1 are the lane's
 // addresses for pixels 8g+q and 8g+q+4. EXEC must be all ones here.
-__device__ __forceinline__ bf16x8 tr2(lds_char* base, int o0, int o1) {
+template <typename F8>
+__device__ __forceinline__ F8 tr2(lds_char* base, int o0, int o1) {
   s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + o0));
   s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + o1));
   s16x8 s = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, s);
+  return __builtin_bit_cast(F8, s);
 }
 
 // One step of the slab walk: nxr new x rows (padded rows py0 ..) and
@@ -116,12 +121,14 @@ struct Step {
   int n, y0, ngr, py0, nxr;
 };
 
-template <int CT, int KT, bool K4>
+template <typename T, int CT, int KT, bool K4>
 __global__ void __launch_bounds__(kBlock)
-conv3x3_wrw_kernel(const short* __restrict__ x,    // (N,H,W,C) bf16
-                   const short* __restrict__ gy,   // (N,H,W,Kmem) bf16
+conv3x3_wrw_kernel(const short* __restrict__ x,    // (N,H,W,C) as T
+                   const short* __restrict__ gy,   // (N,H,W,Kmem) as T
                    float* __restrict__ ws, int N, int H, int W, int Kmem,
                    int n_slabs, int want_bias) {
+  using E = Elem16<T>;
+  using frag8 = typename E::frag8;
   using G = Cfg<CT, KT>;
   constexpr int C = 16 * CT;
   constexpr int TW = G::TW;
@@ -166,9 +173,9 @@ conv3x3_wrw_kernel(const short* __restrict__ x,    // (N,H,W,C) bf16
       for (int t = 0; t < 9; ++t) acc[a][b][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int b = 0; b < KT; ++b) accb[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const short one = (short)0x3F80;  // bf16 1.0
-  const bf16x8 ones = __builtin_bit_cast(
-      bf16x8, (s16x8{one, one, one, one, one, one, one, one}));
+  const short one = E::kOne;  // 1.0 as T
+  const frag8 ones = __builtin_bit_cast(
+      frag8, (s16x8{one, one, one, one, one, one, one, one}));
 
   s16x8 xv[R * G::XVPR];
   s16x8 gv[R * NGV];
@@ -289,30 +296,29 @@ conv3x3_wrw_kernel(const short* __restrict__ x,    // (N,H,W,C) bf16
         const int row = u >= nch ? 1 : 0;
         const int ch = u - row * nch;
         const int gbase = G::X_BYTES + row * G::GROW + ch * 1024;
-        bf16x8 a[KT];
+        frag8 a[KT];
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt)
-          a[kt] = tr2(lds, gbase + kt * G::GS + loff[0][0],
+          a[kt] = tr2<frag8>(lds, gbase + kt * G::GS + loff[0][0],
                       gbase + kt * G::GS + loff[0][1]);
         if (want_bias && cw == 0) {
 #pragma unroll
           for (int kt = 0; kt < KT; ++kt)
-            accb[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                a[kt], ones, accb[kt], 0, 0, 0);
+            accb[kt] = E::mfma(a[kt], ones, accb[kt]);
         }
         // the three dx operands of one (dy, c-group) are read one
         // group ahead of the MFMAs that use them, so the LDS latency
         // runs under the previous group's MFMAs
-        auto load_b = [&](int grp, bf16x8 (&b)[3]) {
+        auto load_b = [&](int grp, frag8 (&b)[3]) {
           const int dy = grp / G::CPW, cp = grp % G::CPW;
           const int cbase =
               ((s.y0 + row + dy) & (XSLOTS - 1)) * G::XROW + ch * 1024 +
               (cw + cp * G::NWC) * G::XS;
 #pragma unroll
           for (int dx = 0; dx < 3; ++dx)
-            b[dx] = tr2(lds, cbase + loff[dx][0], cbase + loff[dx][1]);
+            b[dx] = tr2<frag8>(lds, cbase + loff[dx][0], cbase + loff[dx][1]);
         };
-        bf16x8 bq[2][3];
+        frag8 bq[2][3];
         load_b(0, bq[0]);
 #pragma unroll
         for (int grp = 0; grp < 3 * G::CPW; ++grp) {
@@ -322,10 +328,8 @@ conv3x3_wrw_kernel(const short* __restrict__ x,    // (N,H,W,C) bf16
           for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
             for (int kt = 0; kt < KT; ++kt)
-              acc[cp][kt][dy * 3 + dx] =
-                  __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                      a[kt], bq[grp & 1][dx], acc[cp][kt][dy * 3 + dx], 0, 0,
-                      0);
+              acc[cp][kt][dy * 3 + dx] = E::mfma(
+                  a[kt], bq[grp & 1][dx], acc[cp][kt][dy * 3 + dx]);
         }
       }
     };
@@ -456,26 +460,15 @@ extern "C" void mine_conv3x3_wrw_plan(int C, int Kmem, int64_t rows,
   *ws_floats = (int64_t)s * *nkb * (CT * KT * 9 + KT) * 256;
 }
 
-// x (N,H,W,C), gy (N,H,W,Kmem) bf16 -> dw (K,C,3,3) fp32 and, where db
-// is not null, db (K) fp32. Kmem is 4 or a multiple of 8 with
-// Kmem >= K; ws comes from mine_conv3x3_wrw_plan. Returns 0, -1 if
-// there is no kernel for (C, Kmem), -2 if a launch failed.
-extern "C" int mine_conv3x3_wrw(const void* x, const void* gy, float* ws,
-                                float* dw, float* db, int N, int H, int W,
-                                int C, int Kmem, int K, int slabs,
-                                hipStream_t stream) {
-  if (C % 16 != 0 || C < 16 || C > 64) return -1;
-  if (Kmem != 4 && Kmem % 8 != 0) return -1;
-  const int CT = C / 16, KT = kt_for(CT, Kmem);
-  const bool k4 = Kmem == 4;
-  const int nkb = ((Kmem + 15) / 16 + KT - 1) / KT;
-  const dim3 grid(slabs, nkb);
-  const short* xs = reinterpret_cast<const short*>(x);
-  const short* gs = reinterpret_cast<const short*>(gy);
-  const int wb = db != nullptr;
+namespace {
+template <typename T>
+void wrw_launch_t(const short* xs, const short* gs, float* ws, int N, int H,
+                  int W, int Kmem, int CT, int KT, bool k4, dim3 grid,
+                  int slabs, int wb, hipStream_t stream) {
 #define WRW_LAUNCH(ct, kt, k4v)                                              \
-  hipLaunchKernelGGL((conv3x3_wrw_kernel<ct, kt, k4v>), grid, dim3(kBlock),  \
-                     0, stream, xs, gs, ws, N, H, W, Kmem, slabs, wb)
+  hipLaunchKernelGGL((conv3x3_wrw_kernel<T, ct, kt, k4v>), grid,             \
+                     dim3(kBlock), 0, stream, xs, gs, ws, N, H, W, Kmem,     \
+                     slabs, wb)
 #define WRW_CT(ct)                                                           \
   if (k4) WRW_LAUNCH(ct, 1, true);                                           \
   else if (KT == 1) WRW_LAUNCH(ct, 1, false);                                \
@@ -489,6 +482,33 @@ extern "C" int mine_conv3x3_wrw(const void* x, const void* gy, float* ws,
   }
 #undef WRW_CT
 #undef WRW_LAUNCH
+}
+}  // namespace
+
+// x (N,H,W,C), gy (N,H,W,Kmem), both bf16 or (is_f16) both fp16 -> dw
+// (K,C,3,3) fp32 and, where db is not null, db (K) fp32. Kmem is 4 or a
+// multiple of 8 with Kmem >= K; ws comes from mine_conv3x3_wrw_plan.
+// Returns 0, -1 if there is no kernel for (C, Kmem), -2 if a launch
+// failed.
+extern "C" int mine_conv3x3_wrw(const void* x, const void* gy, float* ws,
+                                float* dw, float* db, int N, int H, int W,
+                                int C, int Kmem, int K, int slabs, int is_f16,
+                                hipStream_t stream) {
+  if (C % 16 != 0 || C < 16 || C > 64) return -1;
+  if (Kmem != 4 && Kmem % 8 != 0) return -1;
+  const int CT = C / 16, KT = kt_for(CT, Kmem);
+  const bool k4 = Kmem == 4;
+  const int nkb = ((Kmem + 15) / 16 + KT - 1) / KT;
+  const dim3 grid(slabs, nkb);
+  const short* xs = reinterpret_cast<const short*>(x);
+  const short* gs = reinterpret_cast<const short*>(gy);
+  const int wb = db != nullptr;
+  if (is_f16)
+    wrw_launch_t<_Float16>(xs, gs, ws, N, H, W, Kmem, CT, KT, k4, grid, slabs,
+                           wb, stream);
+  else
+    wrw_launch_t<__hip_bfloat16>(xs, gs, ws, N, H, W, Kmem, CT, KT, k4, grid,
+                                 slabs, wb, stream);
   if (hipGetLastError() != hipSuccess) return -2;
   const int n_vec = nkb * (CT * KT * 9 + KT) * 64;
   hipLaunchKernelGGL(conv3x3_wrw_finish_kernel, dim3((n_vec + 15) / 16),

@@ -42,7 +42,8 @@ def mpi_head_pack(conv_out: torch.Tensor, B: int, S: int,
     """
     BS, C, H, W = conv_out.shape
     assert C == 4 and BS == B * S
-    if conv_out.is_cuda and conv_out.dtype in (torch.float32, torch.bfloat16) \
+    if conv_out.is_cuda and conv_out.dtype in (
+            torch.float32, torch.bfloat16, torch.float16) \
             and conv_out.is_contiguous(memory_format=torch.channels_last):
         z_flat = conv_out.permute(0, 2, 3, 1).reshape(-1)  # zero-copy view
         out = _MPIHeadFn.apply(z_flat, BS * H * W, use_alpha)

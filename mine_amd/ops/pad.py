@@ -60,7 +60,8 @@ class _ReflectPadFn(torch.autograd.Function):
 
 def reflection_pad2d(x: torch.Tensor, pad: int = 1) -> torch.Tensor:
     """Reflection-pad a Bx C x H x W tensor by `pad` on every side."""
-    if x.is_cuda and x.dtype in (torch.float32, torch.bfloat16):
+    if x.is_cuda and x.dtype in (torch.float32, torch.bfloat16,
+                                 torch.float16):
         return _ReflectPadFn.apply(x, pad)
     return F.pad(x, (pad, pad, pad, pad), mode="reflect")
 

@@ -3,7 +3,7 @@
 The decoder's five up-stages (ref network/monodepth2/layers.py:198-201)
 are pure memory streams; torch's channels_last nearest kernel measured
 ~15x off the HBM roofline at the flagship shapes. GPU channels_last
-bf16/f32 tensors run on the widened HIP kernels
+bf16/fp16/f32 tensors run on the widened HIP kernels
 (ops/csrc/resample_kernels.hip); everything else falls back to
 F.interpolate.
 """
@@ -37,8 +37,9 @@ class _Upsample2xFn(torch.autograd.Function):
 
 def upsample_nearest2x(x: torch.Tensor) -> torch.Tensor:
     """(B,C,H,W) -> (B,C,2H,2W), nearest."""
-    vec = 8 if x.dtype == torch.bfloat16 else 4
-    if (x.is_cuda and x.dtype in (torch.bfloat16, torch.float32)
+    vec = 8 if x.element_size() == 2 else 4  # 16-byte channel vector
+    if (x.is_cuda
+            and x.dtype in (torch.bfloat16, torch.float16, torch.float32)
             and x.shape[1] % vec == 0
             and x.is_contiguous(memory_format=torch.channels_last)):
         return _Upsample2xFn.apply(x)

@@ -1,6 +1,7 @@
 """Standalone timing of the fused BN kernels at the flagship shapes.
 
     python tools/bn_bench.py [--root OTHER_CHECKOUT] [--deterministic]
+                             [--dtype {bf16,fp16}]
 
 --root imports mine_amd from another built checkout, so two builds can be
 timed with the same shape list. --deterministic runs the module in
@@ -12,11 +13,14 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--root", default=os.path.dirname(
     os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument("--deterministic", action="store_true")
+ap.add_argument("--dtype", choices=("bf16", "fp16"), default="bf16")
 args = ap.parse_args()
 sys.path.insert(0, args.root)
 import torch
 from mine_amd.ops.backend import get_extension
 from mine_amd.ops.bn import FusedBNAct, _ACT
+
+DTYPE = torch.float16 if args.dtype == "fp16" else torch.bfloat16
 
 if args.deterministic:
     from mine_amd.ops.backend import set_deterministic
@@ -47,11 +51,12 @@ def tm(fn, n=10):
     return (time.perf_counter() - t0) / n * 1000
 
 ext = get_extension(required=True)
-print("mode:", "deterministic" if args.deterministic else "default")
+print("mode:", "deterministic" if args.deterministic else "default",
+      " dtype:", args.dtype)
 tot = tot_s = tot_r = 0.0
 for (N, C, H, W) in SHAPES:
     bn = FusedBNAct(C, act="elu").cuda().train()
-    x = torch.randn(N, C, H, W, device="cuda:0", dtype=torch.bfloat16
+    x = torch.randn(N, C, H, W, device="cuda:0", dtype=DTYPE
                     ).contiguous(memory_format=torch.channels_last
                     ).requires_grad_(True)
     gy = torch.randn_like(x)
@@ -65,7 +70,7 @@ for (N, C, H, W) in SHAPES:
     M = N * H * W
     xf = x.detach().permute(0, 2, 3, 1).reshape(-1)
     gf = gy.permute(0, 2, 3, 1).reshape(-1)
-    none = torch.empty(0, device="cuda:0", dtype=torch.bfloat16)
+    none = torch.empty(0, device="cuda:0", dtype=DTYPE)
     rm, rv = torch.zeros(C, device="cuda:0"), torch.ones(C, device="cuda:0")
     ga, be = bn.weight.detach().float(), bn.bias.detach().float()
     mean, invstd = ext.bn_stats(xf, M, C, rm, rv, 1e-5, 0.1, 0, *DET)

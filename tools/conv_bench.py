@@ -2,6 +2,7 @@
 flagship decoder's eight layers, as effective bandwidth.
 
     python tools/conv_bench.py [--root OTHER_CHECKOUT] [--miopen]
+                               [--dtype {bf16,fp16}]
 
 Times are device-event medians. Effective TB/s = compulsory bytes / time,
 the bytes computed here from the shapes: the forward reads x and writes
@@ -20,12 +21,15 @@ ap.add_argument("--root", default=os.path.dirname(
     os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument("--miopen", action="store_true")
 ap.add_argument("--reps", type=int, default=9)
+ap.add_argument("--dtype", choices=("bf16", "fp16"), default="bf16")
 args = ap.parse_args()
 sys.path.insert(0, args.root)
 import torch
 import torch.nn.functional as F
 from mine_amd.ops.backend import get_extension
 from mine_amd.ops.conv import conv3x3_reflect, conv3x3_bwd_data
+
+DTYPE = torch.float16 if args.dtype == "fp16" else torch.bfloat16
 
 N = 256  # B*S of the flagship config
 SHAPES = [  # (name, C, H, W, K)
@@ -62,29 +66,30 @@ _BN_RATE = {}
 
 
 def bn_rate(nbytes):
-    """TB/s of bn_act_fwd (1 read + 1 write) on a bf16 tensor of nbytes."""
+    """TB/s of bn_act_fwd (1 read + 1 write) on a DTYPE tensor of nbytes."""
     if nbytes not in _BN_RATE:
         ext = get_extension(required=True)
         C = 16
         M = nbytes // (2 * C)
-        x = torch.randn(M * C, device="cuda:0", dtype=torch.bfloat16)
+        x = torch.randn(M * C, device="cuda:0", dtype=DTYPE)
         z = torch.zeros(C, device="cuda:0")
         o = torch.ones(C, device="cuda:0")
-        res = torch.empty(0, device="cuda:0", dtype=torch.bfloat16)
+        res = torch.empty(0, device="cuda:0", dtype=DTYPE)
         t = tm(lambda: ext.bn_act_fwd(x, res, z, o, o, z, M, C, 3), args.reps)
         _BN_RATE[nbytes] = 2 * nbytes / t / 1e9
     return _BN_RATE[nbytes]
 
 
 reps = max(args.reps, 8)
+print(f"dtype {args.dtype}")
 tot = {"fwd": 0.0, "bwd": 0.0}
 print(f"{'layer':<16} {'C->K':>7} {'HxW':>9} | {'fwd ms':>7} {'TB/s':>5} "
       f"{'ceil':>5} {'%':>4} | {'bwdD ms':>7} {'TB/s':>5} {'ceil':>5} {'%':>4}")
 for (name, C, H, W, K) in SHAPES:
-    x = torch.randn(N, C, H, W, device="cuda:0", dtype=torch.bfloat16
+    x = torch.randn(N, C, H, W, device="cuda:0", dtype=DTYPE
                     ).contiguous(memory_format=torch.channels_last)
     w = torch.randn(K, C, 3, 3, device="cuda:0") * 0.2
-    gy = torch.randn(N, K, H, W, device="cuda:0", dtype=torch.bfloat16
+    gy = torch.randn(N, K, H, W, device="cuda:0", dtype=DTYPE
                      ).contiguous(memory_format=torch.channels_last)
     by_in, by_out = x.numel() * 2, gy.numel() * 2
     with torch.no_grad():
@@ -93,7 +98,7 @@ for (name, C, H, W, K) in SHAPES:
         extra = ""
         if args.miopen:
             xp = F.pad(x, (1, 1, 1, 1), mode="reflect")
-            wb = w.to(torch.bfloat16)
+            wb = w.to(DTYPE)
             t_mf = tm(lambda: F.conv2d(xp, wb), reps)
             extra = f" | miopen fwd {t_mf:7.3f}"
     rate_f = (by_in + by_out) / t_f / 1e9

@@ -2,6 +2,7 @@
 the flagship decoder's eight layers, as effective bandwidth.
 
     python tools/wrw_bench.py [--root OTHER_CHECKOUT] [--miopen] [--bias]
+                              [--dtype {bf16,fp16}]
 
 Times are device-event medians of the whole binding call (workspace or
 zero fill, the kernel, the finishing kernel). Effective TB/s = compulsory
@@ -22,11 +23,14 @@ ap.add_argument("--root", default=os.path.dirname(
 ap.add_argument("--miopen", action="store_true")
 ap.add_argument("--bias", action="store_true")
 ap.add_argument("--reps", type=int, default=9)
+ap.add_argument("--dtype", choices=("bf16", "fp16"), default="bf16")
 args = ap.parse_args()
 sys.path.insert(0, args.root)
 import torch
 import torch.nn.functional as F
 from mine_amd.ops.backend import get_extension
+
+DTYPE = torch.float16 if args.dtype == "fp16" else torch.bfloat16
 
 N = 256  # B*S of the flagship config
 SHAPES = [  # (name, C, H, W, K)
@@ -63,14 +67,14 @@ _BN_RATE = {}
 
 
 def bn_rate(nbytes):
-    """TB/s of bn_act_fwd (1 read + 1 write) on a bf16 tensor of nbytes."""
+    """TB/s of bn_act_fwd (1 read + 1 write) on a DTYPE tensor of nbytes."""
     if nbytes not in _BN_RATE:
         C = 16
         M = nbytes // (2 * C)
-        x = torch.randn(M * C, device="cuda:0", dtype=torch.bfloat16)
+        x = torch.randn(M * C, device="cuda:0", dtype=DTYPE)
         z = torch.zeros(C, device="cuda:0")
         o = torch.ones(C, device="cuda:0")
-        res = torch.empty(0, device="cuda:0", dtype=torch.bfloat16)
+        res = torch.empty(0, device="cuda:0", dtype=DTYPE)
         t = tm(lambda: ext.bn_act_fwd(x, res, z, o, o, z, M, C, 3), args.reps)
         _BN_RATE[nbytes] = 2 * nbytes / t / 1e9
     return _BN_RATE[nbytes]
@@ -82,13 +86,13 @@ if args.bias:
     call = ext.conv3x3_wrw_bias   # an error on builds without it
 reps = max(args.reps, 8)
 total = total_mi = 0.0
-print(f"root {args.root}  binding {call.__name__}")
+print(f"root {args.root}  binding {call.__name__}  dtype {args.dtype}")
 print(f"{'layer':<16} {'C->K':>7} {'HxW':>9} | {'wrw ms':>7} {'GB':>5} "
       f"{'TB/s':>5} {'ceil':>5} {'%':>4}")
 for (name, C, H, W, K) in SHAPES:
-    x = torch.randn(N, C, H, W, device="cuda:0", dtype=torch.bfloat16
+    x = torch.randn(N, C, H, W, device="cuda:0", dtype=DTYPE
                     ).contiguous(memory_format=torch.channels_last)
-    gy = torch.randn(N, K, H, W, device="cuda:0", dtype=torch.bfloat16
+    gy = torch.randn(N, K, H, W, device="cuda:0", dtype=DTYPE
                      ).contiguous(memory_format=torch.channels_last)
     xf = x.permute(0, 2, 3, 1).reshape(-1)
     gf = gy.permute(0, 2, 3, 1).reshape(-1)
@@ -99,7 +103,7 @@ for (name, C, H, W, K) in SHAPES:
     extra = ""
     if args.miopen:
         xp = F.pad(x, (1, 1, 1, 1), mode="reflect")
-        w = torch.randn(K, C, 3, 3, device="cuda:0", dtype=torch.bfloat16)
+        w = torch.randn(K, C, 3, 3, device="cuda:0", dtype=DTYPE)
         t_mi = tm(lambda: torch.ops.aten.convolution_backward(
             gy, xp, w, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
             [False, True, False]), reps)
