@@ -58,13 +58,14 @@ eav2_fwd_kernel(const float* __restrict__ disp,  // (B,H,W)
        i += gridDim.x * kBlock) {
     const int y = i / W;
     const int x = i - y * W;
-    const float d0 = db[i] * inv_m;
+    // difference first, then the scale: see eav2_bwd_gd_kernel
+    const float d0 = db[i];
     if (x + 1 < W) {
-      sx += fabsf(d0 - db[i + 1] * inv_m) *
+      sx += fabsf((d0 - db[i + 1]) * inv_m) *
             __expf(-img_gx(img, b_off, isc, isy, isx, y, x));
     }
     if (y + 1 < H) {
-      sy += fabsf(d0 - db[i + W] * inv_m) *
+      sy += fabsf((d0 - db[i + W]) * inv_m) *
             __expf(-img_gy(img, b_off, isc, isy, isx, y, x));
     }
   }
@@ -103,30 +104,36 @@ eav2_bwd_gd_kernel(const float* __restrict__ disp,
   const int HW = H * W;
   const float nx = 1.0f / ((float)B * H * (W - 1));
   const float ny = 1.0f / ((float)B * (H - 1) * W);
+  const float sm = inv_m < 0.f ? -1.f : 1.f;
   float tpart = 0.0f;
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < HW;
        i += gridDim.x * kBlock) {
     const int y = i / W;
     const int x = i - y * W;
-    const float d0 = db[i] * inv_m;
+    // The sign comes from the difference of the RAW disparities (exact
+    // in sign, exactly 0 at a tie). d0*inv_m - d1*inv_m contracts to
+    // fma(-d1, inv_m, round(d0*inv_m)), which at d0 == d1 returns the
+    // rounding error of the first product: a tie then gets sgn = +-1
+    // and a full-size spurious gradient. sm keeps the sign of the scale.
+    const float d0 = db[i];
     float g = 0.0f;
     if (x + 1 < W) {  // right edge term (i is the left element)
-      const float diff = d0 - db[i + 1] * inv_m;
+      const float diff = (d0 - db[i + 1]) * sm;
       const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
       g += sgn * __expf(-img_gx(img, b_off, isc, isy, isx, y, x)) * nx;
     }
     if (x > 0) {      // left edge term (i is the right element)
-      const float diff = db[i - 1] * inv_m - d0;
+      const float diff = (db[i - 1] - d0) * sm;
       const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
       g -= sgn * __expf(-img_gx(img, b_off, isc, isy, isx, y, x - 1)) * nx;
     }
     if (y + 1 < H) {
-      const float diff = d0 - db[i + W] * inv_m;
+      const float diff = (d0 - db[i + W]) * sm;
       const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
       g += sgn * __expf(-img_gy(img, b_off, isc, isy, isx, y, x)) * ny;
     }
     if (y > 0) {
-      const float diff = db[i - W] * inv_m - d0;
+      const float diff = (db[i - W] - d0) * sm;
       const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
       g -= sgn * __expf(-img_gy(img, b_off, isc, isy, isx, y - 1, x)) * ny;
     }
