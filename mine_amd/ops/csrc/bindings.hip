@@ -214,6 +214,8 @@ std::vector<at::Tensor> tgt_composite_fwd(at::Tensor mpi, at::Tensor hinv,
   TORCH_CHECK(mpi.dim() == 5 && mpi.size(4) == 4, "mpi must be (B,S,H,W,4)");
   const int B = mpi.size(0), S = mpi.size(1), H = mpi.size(2), W = mpi.size(3);
   TORCH_CHECK(S <= 192, "S too large for the LDS geometry stage");
+  TORCH_CHECK((int64_t)H * W * 4 < (int64_t(1) << 31),
+              "one plane must stay below 2^31 floats (32-bit tap offsets)");
   TORCH_CHECK(hinv.sizes() == at::IntArrayRef({B, S, 3, 3}));
   auto rgb = at::empty({B, 3, H, W}, mpi.options());
   auto depth = at::empty({B, 1, H, W}, mpi.options());
@@ -231,18 +233,34 @@ std::vector<at::Tensor> tgt_composite_fwd(at::Tensor mpi, at::Tensor hinv,
 // per-plane payloads, a per-src-tile gather kernel inverts the map
 // (hfwd required). mode 0: the round-1 all-atomic scatter (kept for
 // A/B tests and as a fallback).
+// workspace (trailing, default none = allocate here) is the mode-1
+// payload buffer, same shape as mpi. Its contents on entry do not
+// matter: the backward kernel writes every entry before the gather
+// kernel reads it, so it is at::empty here and a test may hand in a
+// NaN-filled one.
 at::Tensor tgt_composite_bwd(at::Tensor mpi, at::Tensor hinv, at::Tensor hfwd,
                              at::Tensor m, at::Tensor tvec, at::Tensor depths,
                              bool bg_inf, bool alpha, at::Tensor g_rgb,
-                             at::Tensor g_depth, int64_t mode) {
+                             at::Tensor g_depth, int64_t mode,
+                             c10::optional<at::Tensor> workspace) {
   CHECK_IN(mpi);
   const int B = mpi.size(0), S = mpi.size(1), H = mpi.size(2), W = mpi.size(3);
+  TORCH_CHECK((int64_t)H * W * 4 < (int64_t(1) << 31),
+              "one plane must stay below 2^31 floats (32-bit tap offsets)");
   auto grad_mpi = at::zeros_like(mpi);
   at::Tensor payload;
   float* pay_ptr = nullptr;
   if (mode == 1) {
     TORCH_CHECK(hfwd.numel() == (int64_t)B * S * 9, "hfwd required in gather mode");
-    payload = at::zeros_like(mpi);
+    if (workspace.has_value()) {
+      payload = *workspace;
+      CHECK_IN(payload);
+      TORCH_CHECK(payload.numel() == mpi.numel() &&
+                  payload.device() == mpi.device(),
+                  "workspace must match mpi in size and device");
+    } else {
+      payload = at::empty_like(mpi);
+    }
     pay_ptr = payload.data_ptr<float>();
   }
   mine_tgt_composite_bwd(mpi.data_ptr<float>(), hinv.data_ptr<float>(),
@@ -901,7 +919,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("src_composite_bwd", &src_composite_bwd);
   mod.def("tgt_composite_fwd", &tgt_composite_fwd,
           "fused plane-sweep warp + z-cull + composite, forward");
-  mod.def("tgt_composite_bwd", &tgt_composite_bwd);
+  mod.def("tgt_composite_bwd", &tgt_composite_bwd, pybind11::arg("mpi"),
+          pybind11::arg("hinv"), pybind11::arg("hfwd"), pybind11::arg("m"),
+          pybind11::arg("tvec"), pybind11::arg("depths"),
+          pybind11::arg("bg_inf"), pybind11::arg("alpha"),
+          pybind11::arg("g_rgb"), pybind11::arg("g_depth"),
+          pybind11::arg("mode"), pybind11::arg("workspace") = pybind11::none());
   mod.def("ssim_fwd", &ssim_fwd);
   mod.def("ssim_bwd", &ssim_bwd);
   mod.def("eav2_fwd", &eav2_fwd, "fused edge-aware smoothness v2 fwd");

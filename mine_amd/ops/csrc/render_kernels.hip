@@ -351,62 +351,94 @@ DEV TapRef make_tap(float u, float v, int W, int H) {
   return t;
 }
 
-// Shared projective map, noinline: the scatter pass and the gather
-// kernel must classify taps from BITWISE-identical (u, v) — separate
-// inlining contexts could contract FMAs differently and flip a
-// floor()/interior decision at an integer boundary, silently dropping
-// one pixel's gradient.
-__device__ __attribute__((noinline)) float2
-project_uv(const float* __restrict__ Hrow, int x, int y) {
-  const float hx = Hrow[0] * x + Hrow[1] * y + Hrow[2];
-  const float hy = Hrow[3] * x + Hrow[4] * y + Hrow[5];
-  const float hz = Hrow[6] * x + Hrow[7] * y + Hrow[8];
+// CONTRACTION RULE. The per-plane functions below (project_uv,
+// bilinear4, sample_plane, plane_delta, tgt_plane_terms) are inlined
+// into several contexts that must see BITWISE-identical values:
+//  * pass A and pass B of the backward telescope fp64 sums of the same
+//    fp32 terms against each other and divide the residue by u ~ 1e-6;
+//    a last-bit difference in a term becomes an O(0.1) sigma gradient;
+//  * the backward kernel and the gather kernel classify taps from the
+//    same (u, v); a different rounding flips a floor()/interior decision
+//    at an integer boundary and silently drops one pixel's gradient.
+// The compiler decides FMA contraction per inlining context, so each of
+// these functions switches it off for its own body and writes every
+// fused operation as an explicit fmaf. What is fused is then fixed in
+// the source, and no call, scratch or out-parameter is needed to pin
+// it. A helper called from them must follow the same rule or hold no
+// contractible expression (clampf, make_tap).
+DEV float2 project_uv(const float* Hrow, int x, int y) {
+#pragma clang fp contract(off)
+  const float fx = (float)x, fy = (float)y;
+  const float hx = fmaf(Hrow[0], fx, fmaf(Hrow[1], fy, Hrow[2]));
+  const float hy = fmaf(Hrow[3], fx, fmaf(Hrow[4], fy, Hrow[5]));
+  const float hz = fmaf(Hrow[6], fx, fmaf(Hrow[7], fy, Hrow[8]));
   const float iz = 1.0f / hz;
   return make_float2(hx * iz, hy * iz);
 }
 
-DEV float4 bilinear4(const float* base, const TapRef& t, int W) {
-  const float4 p00 = *reinterpret_cast<const float4*>(base + ((int64_t)t.y0 * W + t.x0) * 4);
-  const float4 p01 = *reinterpret_cast<const float4*>(base + ((int64_t)t.y0 * W + t.x1) * 4);
-  const float4 p10 = *reinterpret_cast<const float4*>(base + ((int64_t)t.y1 * W + t.x0) * 4);
-  const float4 p11 = *reinterpret_cast<const float4*>(base + ((int64_t)t.y1 * W + t.x1) * 4);
-  const float w00 = (1 - t.wx) * (1 - t.wy), w01 = t.wx * (1 - t.wy);
-  const float w10 = (1 - t.wx) * t.wy, w11 = t.wx * t.wy;
-  return make_float4(w00 * p00.x + w01 * p01.x + w10 * p10.x + w11 * p11.x,
-                     w00 * p00.y + w01 * p01.y + w10 * p10.y + w11 * p11.y,
-                     w00 * p00.z + w01 * p01.z + w10 * p10.z + w11 * p11.z,
-                     w00 * p00.w + w01 * p01.w + w10 * p10.w + w11 * p11.w);
+// no border clamping: u in [0, W-1], v in [0, H-1] (TapRef::interior)
+DEV bool uv_interior(float u, float v, int W, int H) {
+  return (u == clampf(u, 0.0f, (float)(W - 1))) &&
+         (v == clampf(v, 0.0f, (float)(H - 1)));
 }
 
-// One plane's warped sample: rgb+sigma (z-culled), analytic point, validity.
+// `base` is one plane (wave-uniform); the tap offsets are 32-bit (the
+// bindings check H*W*4 < 2^31), so the loads address as uniform base +
+// per-lane offset and hold no 64-bit pointers in vector registers.
+DEV float4 bilinear4(const float* base, const TapRef& t, int W) {
+#pragma clang fp contract(off)
+  const float4 p00 = *reinterpret_cast<const float4*>(base + (unsigned)(t.y0 * W + t.x0) * 4u);
+  const float4 p01 = *reinterpret_cast<const float4*>(base + (unsigned)(t.y0 * W + t.x1) * 4u);
+  const float4 p10 = *reinterpret_cast<const float4*>(base + (unsigned)(t.y1 * W + t.x0) * 4u);
+  const float4 p11 = *reinterpret_cast<const float4*>(base + (unsigned)(t.y1 * W + t.x1) * 4u);
+  const float w00 = (1 - t.wx) * (1 - t.wy), w01 = t.wx * (1 - t.wy);
+  const float w10 = (1 - t.wx) * t.wy, w11 = t.wx * t.wy;
+#define BL(C) fmaf(w11, p11.C, fmaf(w10, p10.C, fmaf(w01, p01.C, w00 * p00.C)))
+  return make_float4(BL(x), BL(y), BL(z), BL(w));
+#undef BL
+}
+
+// One plane's warped sample: rgb+sigma (z-culled), analytic point,
+// validity, and the projected (u, v) the taps were made from (pass B
+// rebuilds the TapRef from them where it scatters).
 struct PlaneSample {
   float4 rgbs;
   float3 v;
   float inb;
+  float pu, pv;
 };
 
-__device__ __attribute__((noinline)) PlaneSample
-sample_plane(const float* __restrict__ mpi_b, int s, int HW,
-                             const float* __restrict__ s_geom, float d,
+DEV PlaneSample sample_plane(const float* mpi_b, int s, int HW,
+                             const float* s_geom, float d,
                              const float3x3& M, float3 tv,
-                             int x, int y, int W, int H, TapRef* tap_out) {
-  const float* Hrow = s_geom + s * 9;
-  const float2 uv = project_uv(Hrow, x, y);
+                             int x, int y, int W, int H) {
+#pragma clang fp contract(off)
+  const float2 uv = project_uv(s_geom + s * 9, x, y);
   const float u = uv.x, v = uv.y;
 
   PlaneSample ps;
+  ps.pu = u;
+  ps.pv = v;
   ps.inb = (u > -1.0f && u < (float)W && v > -1.0f && v < (float)H) ? 1.0f : 0.0f;
 
   const TapRef tap = make_tap(u, v, W, H);
-  if (tap_out) *tap_out = tap;
   ps.rgbs = bilinear4(mpi_b + (int64_t)s * HW * 4, tap, W);
 
   const float ucl = clampf(u, 0.0f, (float)(W - 1));
   const float vcl = clampf(v, 0.0f, (float)(H - 1));
-  const float3 r = M.mul(ucl, vcl, 1.0f);
-  ps.v = make_float3(r.x * d + tv.x, r.y * d + tv.y, r.z * d + tv.z);
+  const float rx = fmaf(M.m[0], ucl, fmaf(M.m[1], vcl, M.m[2]));
+  const float ry = fmaf(M.m[3], ucl, fmaf(M.m[4], vcl, M.m[5]));
+  const float rz = fmaf(M.m[6], ucl, fmaf(M.m[7], vcl, M.m[8]));
+  ps.v = make_float3(fmaf(rx, d, tv.x), fmaf(ry, d, tv.y), fmaf(rz, d, tv.z));
   if (ps.v.z < 0.0f) ps.rgbs.w = 0.0f;  // z-cull (ref mpi_rendering.py:233-235)
   return ps;
+}
+
+// Inter-plane distance of two warped plane points (contraction rule).
+DEV float plane_delta(float3 a, float3 b) {
+#pragma clang fp contract(off)
+  const float dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
+  return sqrtf(fmaf(dz, dz, fmaf(dy, dy, dx * dx)));
 }
 
 template <bool BG_INF, bool ALPHA = false>
@@ -443,7 +475,7 @@ tgt_composite_fwd_kernel(const float* __restrict__ mpi,
     float3 R = make_float3(0.f, 0.f, 0.f);
 
     PlaneSample cur = sample_plane(mpi_b, 0, HW, s_geom, s_depth[0], M, tv,
-                                   x, y, W, H, nullptr);
+                                   x, y, W, H);
     mask += cur.inb;
     int s = 0;
     for (; s < S; ++s) {
@@ -451,11 +483,9 @@ tgt_composite_fwd_kernel(const float* __restrict__ mpi,
       PlaneSample nxt;
       if (s + 1 < S) {
         nxt = sample_plane(mpi_b, s + 1, HW, s_geom, s_depth[s + 1], M, tv,
-                           x, y, W, H, nullptr);
+                           x, y, W, H);
         mask += nxt.inb;
-        const float dx = nxt.v.x - cur.v.x, dy = nxt.v.y - cur.v.y,
-                    dz = nxt.v.z - cur.v.z;
-        delta = sqrtf(dx * dx + dy * dy + dz * dz);
+        delta = plane_delta(cur.v, nxt.v);
       } else {
         delta = 1e3f;
       }
@@ -475,12 +505,8 @@ tgt_composite_fwd_kernel(const float* __restrict__ mpi,
     // mask still counts EVERY plane's validity (ref mpi_rendering.py:239):
     // projection-only tail, no MPI gathers
     for (int s2 = s + 1; s2 < S; ++s2) {
-      const float* Hrow = s_geom + s2 * 9;
-      const float hx = Hrow[0] * x + Hrow[1] * y + Hrow[2];
-      const float hy = Hrow[3] * x + Hrow[4] * y + Hrow[5];
-      const float hz = Hrow[6] * x + Hrow[7] * y + Hrow[8];
-      const float iz = 1.0f / hz;
-      const float u = hx * iz, v = hy * iz;
+      const float2 uv = project_uv(s_geom + s2 * 9, x, y);
+      const float u = uv.x, v = uv.y;
       mask += (u > -1.0f && u < (float)W && v > -1.0f && v < (float)H)
                   ? 1.0f : 0.0f;
     }
@@ -498,10 +524,10 @@ tgt_composite_fwd_kernel(const float* __restrict__ mpi,
 DEV void scatter4(float* base, const TapRef& t, int W, float4 g) {
   const float w00 = (1 - t.wx) * (1 - t.wy), w01 = t.wx * (1 - t.wy);
   const float w10 = (1 - t.wx) * t.wy, w11 = t.wx * t.wy;
-  float* p00 = base + ((int64_t)t.y0 * W + t.x0) * 4;
-  float* p01 = base + ((int64_t)t.y0 * W + t.x1) * 4;
-  float* p10 = base + ((int64_t)t.y1 * W + t.x0) * 4;
-  float* p11 = base + ((int64_t)t.y1 * W + t.x1) * 4;
+  float* p00 = base + (unsigned)(t.y0 * W + t.x0) * 4u;
+  float* p01 = base + (unsigned)(t.y0 * W + t.x1) * 4u;
+  float* p10 = base + (unsigned)(t.y1 * W + t.x0) * 4u;
+  float* p11 = base + (unsigned)(t.y1 * W + t.x1) * 4u;
 #define SC(P, WGT)                                  \
   if (WGT != 0.0f) {                                \
     atomicAdd(P + 0, WGT * g.x);                    \
@@ -513,31 +539,23 @@ DEV void scatter4(float* base, const TapRef& t, int W, float4 g) {
 #undef SC
 }
 
-// Per-plane inter-plane distance — noinline so both backward passes get
-// bitwise-identical values (exact-cancellation requirement, see
-// src_plane_term).
-__device__ __attribute__((noinline)) float plane_delta(float3 a, float3 b) {
-  const float dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
-  return sqrtf(dx * dx + dy * dy + dz * dz);
-}
-
 // Per-plane backward components for the tgt kernel. e depends on the
 // composite totals (D, Wsum) which are only known after a full pass, but
 // it is LINEAR in them: e = r + qv*vz + qc with pass-independent
 // r = rgb.gR. The suffix sums therefore split into three component sums
 // (cr, cv, cw) accumulated WITHOUT D, and the /u-amplified telescoping
-// stays exact per component because this one noinline instance feeds
-// both passes bitwise-identical terms.
+// stays exact per component because both passes get bitwise-identical
+// terms (contraction rule above).
 struct TgtTerm {
   float t, r, cr, cv, cw;
 };
 
 template <bool ALPHA>
-__device__ __attribute__((noinline)) TgtTerm
-tgt_plane_terms(float4 rgbs, float vz, float delta, float3 gR) {
+DEV TgtTerm tgt_plane_terms(float4 rgbs, float vz, float delta, float3 gR) {
+#pragma clang fp contract(off)
   TgtTerm o;
   o.t = ALPHA ? (1.0f - rgbs.w) : __expf(-rgbs.w * delta);
-  o.r = rgbs.x * gR.x + rgbs.y * gR.y + rgbs.z * gR.z;
+  o.r = fmaf(rgbs.z, gR.z, fmaf(rgbs.y, gR.y, rgbs.x * gR.x));
   const float omt = 1.0f - o.t;
   o.cr = omt * o.r;
   o.cv = omt * vz;
@@ -547,9 +565,11 @@ tgt_plane_terms(float4 rgbs, float vz, float delta, float3 gR) {
 
 // GATHER mode (the round-2 redesign, docs/NEXT.md 2 / VERDICT item 3):
 // interior target pixels write their per-plane gradient as a PLAIN
-// coalesced float4 into `payload` (B,S,H,W,4, pre-zeroed) instead of a
-// 16-atomic bilinear scatter; only border-clamped pixels (a thin ring
-// per plane) take the atomic path. tgt_gather_kernel then inverts the
+// coalesced float4 into `payload` (B,S,H,W,4) instead of a 16-atomic
+// bilinear scatter; only border-clamped pixels (a thin ring per plane)
+// take the atomic path. `payload` needs no zero fill: the kernel writes
+// every entry, zeros where a pixel is border-clamped or lies behind the
+// dead-transmittance break. tgt_gather_kernel then inverts the
 // map per source tile. Decomposition proven against the scatter form
 // in tests/test_kernel_sim.py::test_warp_backward_gather_decomposition.
 template <bool BG_INF, bool GATHER, bool ALPHA = false>
@@ -562,7 +582,7 @@ tgt_composite_bwd_kernel(const float* __restrict__ mpi,
                          const float* __restrict__ g_rgb,
                          const float* __restrict__ g_depth,
                          float* __restrict__ grad_mpi,  // pre-zeroed
-                         float* __restrict__ payload,   // pre-zeroed (GATHER)
+                         float* __restrict__ payload,   // fully written (GATHER)
                          int B, int S, int H, int W) {
   __shared__ float s_geom[kMaxS * 9];
   __shared__ float s_depth[kMaxS];
@@ -597,13 +617,13 @@ tgt_composite_bwd_kernel(const float* __restrict__ mpi,
     double TaR = 0.0, TaV = 0.0, TaW = 0.0;
     double Ad = 1.0;
     PlaneSample cur = sample_plane(mpi_b, 0, HW, s_geom, s_depth[0], M, tv,
-                                   x, y, W, H, nullptr);
+                                   x, y, W, H);
     for (int s = 0; s < S; ++s) {
       float delta;
       PlaneSample nxt;
       if (s + 1 < S) {
         nxt = sample_plane(mpi_b, s + 1, HW, s_geom, s_depth[s + 1], M, tv,
-                           x, y, W, H, nullptr);
+                           x, y, W, H);
         delta = plane_delta(cur.v, nxt.v);
       } else {
         delta = 1e3f;
@@ -631,16 +651,16 @@ tgt_composite_bwd_kernel(const float* __restrict__ mpi,
     // ---- pass B: emit gradients, bilinear scatter ----
     double prR = 0.0, prV = 0.0, prW = 0.0;
     Ad = 1.0;
-    TapRef tap;
-    cur = sample_plane(mpi_b, 0, HW, s_geom, s_depth[0], M, tv, x, y, W, H,
-                       &tap);
-    for (int s = 0; s < S; ++s) {
+    float* pay_b = GATHER ? payload + (int64_t)b * S * HW * 4 : nullptr;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    cur = sample_plane(mpi_b, 0, HW, s_geom, s_depth[0], M, tv, x, y, W, H);
+    int s = 0;
+    for (; s < S; ++s) {
       float delta;
       PlaneSample nxt;
-      TapRef ntap;
       if (s + 1 < S) {
         nxt = sample_plane(mpi_b, s + 1, HW, s_geom, s_depth[s + 1], M, tv,
-                           x, y, W, H, &ntap);
+                           x, y, W, H);
         delta = plane_delta(cur.v, nxt.v);
       } else {
         delta = 1e3f;
@@ -659,22 +679,39 @@ tgt_composite_bwd_kernel(const float* __restrict__ mpi,
       const double suffix = (TaR - prR) + (double)qv * (TaV - prV) +
                             (double)qc * (TaW - prW);
       const float e = tt.r + qv * cur.v.z + qc;
-      const float dt = -Af * e + (float)(suffix / (double)u);
+      // the exactness requirement is on the fp64 subtractions; dividing
+      // the converted residue by u in fp32 is well conditioned
+      const float dt = -Af * e + (float)suffix / u;
       // culled sigma/alpha contributed nothing -> no gradient through it
       const float dsigma = (cur.v.z < 0.0f)
           ? 0.0f : (ALPHA ? -dt : dt * (-delta * t));
       const float4 g = make_float4(w * gR.x, w * gR.y, w * gR.z, dsigma);
-      if (GATHER && tap.interior) {
-        *reinterpret_cast<float4*>(
-            payload + ((int64_t)b * S + s) * HW * 4 + (int64_t)pix * 4) = g;
-      } else {
-        scatter4(gm_b + (int64_t)s * HW * 4, tap, W, g);
+      // payload is NOT pre-zeroed: this thread writes every (s, pix)
+      // entry it owns — g where the taps are interior, zeros where the
+      // pixel goes through the atomic border path instead
+      const bool interior = GATHER && uv_interior(cur.pu, cur.pv, W, H);
+      if (GATHER) {
+        // per-component selects: a select between two float4 objects
+        // goes through scratch
+        *reinterpret_cast<float4*>(pay_b + (int64_t)s * HW * 4 +
+                                   (unsigned)pix * 4u) =
+            make_float4(interior ? g.x : 0.f, interior ? g.y : 0.f,
+                        interior ? g.z : 0.f, interior ? g.w : 0.f);
+      }
+      if (!interior) {
+        scatter4(gm_b + (int64_t)s * HW * 4,
+                 make_tap(cur.pu, cur.pv, W, H), W, g);
       }
       Ad *= (double)u;
       cur = nxt;
-      tap = ntap;
       // grad_mpi is pre-zeroed; dead-transmittance tail scatters ~0
       if (Ad < 1e-14) break;
+    }
+    if (GATHER) {  // ... and zeros for the planes behind the break
+      for (int s2 = s + 1; s2 < S; ++s2) {
+        *reinterpret_cast<float4*>(pay_b + (int64_t)s2 * HW * 4 +
+                                   (unsigned)pix * 4u) = zero4;
+      }
     }
   }
 }
@@ -687,15 +724,51 @@ tgt_composite_bwd_kernel(const float* __restrict__ mpi,
 // pass has already completed — no concurrent writers).
 // ---------------------------------------------------------------------------
 
-constexpr int GT = 32;  // gather tile side
+// Plain LDS add of an already rounded addend: with contraction off the
+// caller's product cannot fuse into the add, so this path adds the same
+// fp32 addends as the atomic one.
+DEV void lds_add(float* p, float v) {
+#pragma clang fp contract(off)
+  *p = *p + v;
+}
 
-__global__ void __launch_bounds__(kBlock)
+constexpr int GT = 32;      // gather tile side
+constexpr int kGBlock = 64; // ONE wave per tile, see below
+constexpr int kGRows = 4;   // payload rows the wave keeps in flight
+
+// The wave takes bbox rows and its lanes take x (no integer division per
+// pixel); it issues the loads of kGRows rows before it processes them.
+//
+// LDS float atomics are what this kernel used to spend its time on
+// (profiles/r09_warp_bwd.md: 1.98 ms with them, 0.25 ms with plain adds in
+// their place, same loads and arithmetic). So a tile belongs to ONE wave,
+// and a row of target pixels adds its taps with plain LDS read-add-write
+// wherever no two lanes of one instruction can hit the same address:
+//  * one instruction handles one tap kind ((x0,y0), (x1,y0), ...) of the
+//    even or of the odd lanes, so two of its lanes collide only if they
+//    have the same (x0, y0) and are an even number of lanes apart;
+//  * the row qualifies if x0 and y0 are each weakly monotone over the
+//    lanes of the chunk and, within every run of neighbouring lanes that
+//    share one (x0, y0), at most one even and one odd lane add anything.
+//    Two lanes i < j with one (x0, y0) squeeze every lane between them
+//    onto the same (x0, y0), so they lie in one run, which the check
+//    covers; lanes that add nothing (border-clamped, zero payload) do
+//    not disqualify a row. Along an image row a homography moves u and v
+//    monotonically, so rows fail only where the map shrinks below half a
+//    source pixel per target pixel or where rounding makes y0 flicker;
+//    those rows keep the atomics.
+//  * instructions of one wave reach the LDS in order, and nobody else
+//    touches the tile; a wavefront fence between the tap kinds keeps the
+//    compiler from reordering their read-add-writes.
+// The tile is channel-planar (four GT*GT planes): x-adjacent lanes map to
+// x-adjacent source taps, so a channel's adds fall on consecutive banks.
+__global__ void __launch_bounds__(kGBlock)
 tgt_gather_kernel(const float* __restrict__ payload,  // (B,S,H,W,4)
                   const float* __restrict__ hinv,     // (B,S,3,3) tgt->src
                   const float* __restrict__ hfwd,     // (B,S,3,3) src->tgt
                   float* __restrict__ grad_mpi,       // += (B,S,H,W,4)
                   int B, int S, int H, int W, int tiles_x) {
-  __shared__ float s_acc[GT * GT * 4];
+  __shared__ float s_acc[4 * GT * GT];  // [channel][qy][qx]
   __shared__ float s_Hi[9];
   __shared__ float s_Hf[9];
   const int tile = blockIdx.x;
@@ -705,7 +778,7 @@ tgt_gather_kernel(const float* __restrict__ payload,  // (B,S,H,W,4)
   const int ty0 = (tile / tiles_x) * GT;
   const int tid = threadIdx.x;
 
-  for (int i = tid; i < GT * GT * 4; i += kBlock) s_acc[i] = 0.0f;
+  for (int i = tid; i < GT * GT * 4; i += kGBlock) s_acc[i] = 0.0f;
   if (tid < 9) {
     s_Hi[tid] = hinv[((int64_t)b * S + s) * 9 + tid];
     s_Hf[tid] = hfwd[((int64_t)b * S + s) * 9 + tid];
@@ -746,43 +819,110 @@ tgt_gather_kernel(const float* __restrict__ payload,  // (B,S,H,W,4)
   const float* pay_b = payload + ((int64_t)b * S + s) * HW * 4;
 
   if (bw > 0 && bh > 0) {
-    for (int i = tid; i < bw * bh; i += kBlock) {
-      const int px = px0 + i % bw;
-      const int py = py0 + i / bw;
-      const float4 g = *reinterpret_cast<const float4*>(
-          pay_b + ((int64_t)py * W + px) * 4);
-      if (g.x == 0.f && g.y == 0.f && g.z == 0.f && g.w == 0.f) continue;
-      const float2 uv = project_uv(s_Hi, px, py);
-      const TapRef t = make_tap(uv.x, uv.y, W, H);
-      // payload is only written for interior pixels, but re-derive and
-      // skip just in case (bitwise-identical classification via the
-      // shared noinline project_uv)
-      if (!t.interior) continue;
-      const float w00 = (1 - t.wx) * (1 - t.wy), w01 = t.wx * (1 - t.wy);
-      const float w10 = (1 - t.wx) * t.wy, w11 = t.wx * t.wy;
-#define GSC(QX, QY, WGT)                                              \
-      if (WGT != 0.0f && (QX) >= tx0 && (QX) < tx0 + GT &&            \
-          (QY) >= ty0 && (QY) < ty0 + GT) {                           \
-        float* a = s_acc + (((QY) - ty0) * GT + ((QX) - tx0)) * 4;    \
-        atomicAdd(a + 0, WGT * g.x);                                  \
-        atomicAdd(a + 1, WGT * g.y);                                  \
-        atomicAdd(a + 2, WGT * g.z);                                  \
-        atomicAdd(a + 3, WGT * g.w);                                  \
-      }
-      GSC(t.x0, t.y0, w00) GSC(t.x1, t.y0, w01)
-      GSC(t.x0, t.y1, w10) GSC(t.x1, t.y1, w11)
+    const int lane = tid;
+    for (int r0 = 0; r0 < bh; r0 += kGRows) {
+      for (int c0 = 0; c0 < bw; c0 += 64) {
+        const int cx = c0 + lane;
+        const bool in_chunk = cx < bw;
+        const int px = px0 + cx;  // <= W - 1 where in_chunk
+        float4 g[kGRows];
+#pragma unroll
+        for (int k = 0; k < kGRows; ++k) {
+          g[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (in_chunk && r0 + k < bh) {  // py0 + r0 + k <= H - 1
+            g[k] = *reinterpret_cast<const float4*>(
+                pay_b + (unsigned)((py0 + r0 + k) * W + px) * 4u);
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < kGRows; ++k) {
+          if (r0 + k >= bh) break;  // wave-uniform
+          const float4 gk = g[k];
+          const int py = py0 + r0 + k;
+          // every lane projects, also where it adds nothing: the row's
+          // monotonicity is judged on all lanes of the chunk
+          const float2 uv = project_uv(s_Hi, px, py);
+          const TapRef t = make_tap(uv.x, uv.y, W, H);
+          // the backward kernel writes zeros for non-interior pixels,
+          // but re-derive and skip just in case (bitwise-identical
+          // classification: contraction rule of project_uv)
+          const bool adds = in_chunk &&
+              !(gk.x == 0.f && gk.y == 0.f && gk.z == 0.f && gk.w == 0.f) &&
+              uv_interior(uv.x, uv.y, W, H);
+          if (!__any(adds)) continue;  // wave-uniform
+
+          const int x0l = __shfl_up(t.x0, 1), y0l = __shfl_up(t.y0, 1);
+          const bool has_l = in_chunk && lane >= 1;  // left one in_chunk too
+          const bool mono_x = __all(!has_l || t.x0 >= x0l) ||
+                              __all(!has_l || t.x0 <= x0l);
+          const bool mono_y = __all(!has_l || t.y0 >= y0l) ||
+                              __all(!has_l || t.y0 <= y0l);
+          // runs of lanes with one (x0, y0): a lane collides if an adding
+          // lane of its parity sits to its left in its own run
+          const unsigned long long starts =
+              __ballot(!(has_l && t.x0 == x0l && t.y0 == y0l));
+          const unsigned long long addm = __ballot(adds);
+          const unsigned long long upto = (2ull << lane) - 1ull;  // 0..lane
+          const int start = 63 - __clzll((long long)(starts & upto));
+          const unsigned long long left =
+              (upto >> 1) & ~((1ull << start) - 1ull);  // start..lane-1
+          const unsigned long long par = (lane & 1) ? 0xAAAAAAAAAAAAAAAAull
+                                                    : 0x5555555555555555ull;
+          const bool no_dup = __all(!(adds && (addm & left & par) != 0ull));
+          const bool plain = mono_x && mono_y && no_dup;  // wave-uniform
+
+          const float w00 = (1 - t.wx) * (1 - t.wy), w01 = t.wx * (1 - t.wy);
+          const float w10 = (1 - t.wx) * t.wy, w11 = t.wx * t.wy;
+#define GSC(ADD, QX, QY, WGT)                                         \
+          if (WGT != 0.0f && (QX) >= tx0 && (QX) < tx0 + GT &&        \
+              (QY) >= ty0 && (QY) < ty0 + GT) {                       \
+            float* a = s_acc + ((QY) - ty0) * GT + ((QX) - tx0);      \
+            ADD(a + 0 * GT * GT, WGT * gk.x);                         \
+            ADD(a + 1 * GT * GT, WGT * gk.y);                         \
+            ADD(a + 2 * GT * GT, WGT * gk.z);                         \
+            ADD(a + 3 * GT * GT, WGT * gk.w);                         \
+          }
+#define GSC4(ADD)                                                     \
+          GSC(ADD, t.x0, t.y0, w00) TAP_ORDER                         \
+          GSC(ADD, t.x1, t.y0, w01) TAP_ORDER                         \
+          GSC(ADD, t.x0, t.y1, w10) TAP_ORDER                         \
+          GSC(ADD, t.x1, t.y1, w11)
+          // one lane's tap may be the cell of another lane's other tap
+          // kind: keep the kinds' read-add-writes in program order
+#define TAP_ORDER                                                     \
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      \
+          __builtin_amdgcn_wave_barrier();
+#define ADD_PLAIN(P, V) lds_add((P), (V))
+#define ADD_ATOMIC(P, V) atomicAdd((P), (V))
+          if (plain) {
+            if (adds && (lane & 1) == 0) { GSC4(ADD_PLAIN) }
+            // keeps the two halves two instruction streams: without it
+            // merging the identical bodies would be a legal transform
+            TAP_ORDER
+            if (adds && (lane & 1) == 1) { GSC4(ADD_PLAIN) }
+          } else if (adds) {
+            GSC4(ADD_ATOMIC)
+          }
+#undef ADD_ATOMIC
+#undef ADD_PLAIN
+#undef TAP_ORDER
+#undef GSC4
 #undef GSC
+        }
+      }
     }
   }
   __syncthreads();
 
   // ---- flush: plain read-add-write float4 (no concurrent writers) ----
   float* gm = grad_mpi + ((int64_t)b * S + s) * HW * 4;
-  for (int i = tid; i < GT * GT; i += kBlock) {
-    const int qx = tx0 + i % GT;
+  for (int i = tid; i < GT * GT; i += kGBlock) {
+    const int qx = tx0 + (i & (GT - 1));
     const int qy = ty0 + i / GT;
     if (qx >= W || qy >= H) continue;
-    const float4 a = *reinterpret_cast<const float4*>(s_acc + i * 4);
+    const float4 a = make_float4(s_acc[i], s_acc[GT * GT + i],
+                                 s_acc[2 * GT * GT + i],
+                                 s_acc[3 * GT * GT + i]);
     if (a.x == 0.f && a.y == 0.f && a.z == 0.f && a.w == 0.f) continue;
     float4* dst = reinterpret_cast<float4*>(gm + ((int64_t)qy * W + qx) * 4);
     float4 cur = *dst;
@@ -879,7 +1019,7 @@ void mine_tgt_composite_fwd(const float* mpi, const float* hinv,
 }
 
 // mode 0: scatter everywhere (round-1 path); mode 1: gather redesign
-// (payload + hfwd required; payload and grad_mpi pre-zeroed).
+// (payload + hfwd required; grad_mpi pre-zeroed, payload need not be).
 void mine_tgt_composite_bwd(const float* mpi, const float* hinv,
                             const float* hfwd, const float* m_rki,
                             const float* tvec, const float* depths,
@@ -888,7 +1028,7 @@ void mine_tgt_composite_bwd(const float* mpi, const float* hinv,
                             int B, int S, int H, int W, int bg_inf, int mode,
                             int alpha, hipStream_t stream) {
   dim3 grid(grid_x(H * W), B);
-#define TGT_BWD_BODY(BGv, ALv)                                                if (mode == 1) {                                                              hipLaunchKernelGGL((tgt_composite_bwd_kernel<BGv, true, ALv>), grid,                           dim3(kBlock), 0, stream, mpi, hinv, m_rki, tvec,                            depths, g_rgb, g_depth, grad_mpi, payload,                                  B, S, H, W);                                             const int tiles_x = (W + GT - 1) / GT;                                      const int tiles_y = (H + GT - 1) / GT;                                      dim3 ggrid(tiles_x * tiles_y, S, B);                                        hipLaunchKernelGGL(tgt_gather_kernel, ggrid, dim3(kBlock), 0, stream,                          payload, hinv, hfwd, grad_mpi, B, S, H, W, tiles_x);   } else {                                                                      hipLaunchKernelGGL((tgt_composite_bwd_kernel<BGv, false, ALv>), grid,                          dim3(kBlock), 0, stream, mpi, hinv, m_rki, tvec,                            depths, g_rgb, g_depth, grad_mpi, nullptr,                                  B, S, H, W);                                           }
+#define TGT_BWD_BODY(BGv, ALv)                                                if (mode == 1) {                                                              hipLaunchKernelGGL((tgt_composite_bwd_kernel<BGv, true, ALv>), grid,                           dim3(kBlock), 0, stream, mpi, hinv, m_rki, tvec,                            depths, g_rgb, g_depth, grad_mpi, payload,                                  B, S, H, W);                                             const int tiles_x = (W + GT - 1) / GT;                                      const int tiles_y = (H + GT - 1) / GT;                                      dim3 ggrid(tiles_x * tiles_y, S, B);                                        hipLaunchKernelGGL(tgt_gather_kernel, ggrid, dim3(kGBlock), 0, stream,                          payload, hinv, hfwd, grad_mpi, B, S, H, W, tiles_x);   } else {                                                                      hipLaunchKernelGGL((tgt_composite_bwd_kernel<BGv, false, ALv>), grid,                          dim3(kBlock), 0, stream, mpi, hinv, m_rki, tvec,                            depths, g_rgb, g_depth, grad_mpi, nullptr,                                  B, S, H, W);                                           }
   if (alpha) {
     TGT_BWD_BODY(false, true)
     return;
