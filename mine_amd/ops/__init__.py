@@ -19,7 +19,6 @@ they run the pure-torch reference implementations in
 """
 from mine_amd.ops.torch_ref import (  # noqa: F401
     alpha_composite,
-    gather_pixel_by_pxpy,
     make_meshgrid,
     sample_disparity_from_bins,
     sample_disparity_linspace,
@@ -36,6 +35,7 @@ from mine_amd.ops.backend import (  # noqa: F401
     set_deterministic,
 )
 from mine_amd.ops.renderer import render_src_view, render_tgt_view  # noqa: F401
+from mine_amd.ops.sparse import gather_pixel_by_pxpy  # noqa: F401
 from mine_amd.ops.ssim import ssim  # noqa: F401
 from mine_amd.ops.losses import (  # noqa: F401
     edge_aware_loss,

@@ -47,10 +47,14 @@ def has_extension() -> bool:
 # gradient and the igemm weight gradient — combines its partial sums in
 # an order that depends only on the shapes (per-block / per-slice
 # partials in a workspace, summed by a finishing kernel) instead of with
-# fp32 atomics. The forward becomes bit-reproducible, and so does the
-# backward given the same upstream gradient. Not covered: the renderer's
-# warp backward, the SSIM / smoothness loss scalars and the RCCL
-# all-reduce order (docs/NEXT.md section 7).
+# fp32 atomics. Past the network, the novel-view warp backward runs its
+# order-fixed emit + collect form (mode 2), the SSIM / smoothness
+# scalars and the smoothness backward's per-image dot are summed the
+# same workspace way, the sparse-point gather gets an atomic-free
+# backward and the v1 smoothness Sobel is built from slices. One train
+# step on one GPU is then bit-reproducible: losses, gradients, updated
+# parameters. Not covered: the RCCL all-reduce order (docs/NEXT.md
+# section 7).
 #
 # The initial value is read lazily from MINE_DETERMINISTIC=1, the same
 # convention as MINE_TGT_BWD / MINE_CONV_BWD. The autograd functions read
@@ -65,6 +69,12 @@ def is_deterministic() -> bool:
     if _DETERMINISTIC is None:
         import os
         _DETERMINISTIC = os.environ.get("MINE_DETERMINISTIC", "0") == "1"
+        if _DETERMINISTIC:
+            # as training.deterministic does: the convs that stay on the
+            # library (the 7x7 stem's weight gradient) must not pick an
+            # atomic kernel either
+            import torch
+            torch.backends.cudnn.deterministic = True
     return _DETERMINISTIC
 
 

@@ -26,6 +26,8 @@ void mine_tgt_composite_bwd(const float*, const float*, const float*,
                             const float*, const float*, const float*,
                             const float*, const float*, float*, float*,
                             int, int, int, int, int, int, int, hipStream_t);
+void mine_tgt_collect(const float*, const float*, const float*, float*, int,
+                      int, int, int, hipStream_t);
 void mine_conv_igemm_fwd(const void*, const void*, const float*, void*,
                          float*, int64_t, int, int, int, int, int, int, int,
                          int, int, int, int, int, int, int, int, int,
@@ -34,12 +36,15 @@ int mine_conv_igemm_wrw_slabs(int64_t, int, int, int, int);
 void mine_conv_igemm_wrw(const void*, const void*, float*, float*, int64_t,
                          int, int, int, int, int, int, int, int, int, int,
                          int, int, int, int, hipStream_t);
-void mine_eav2_fwd(const float*, const float*, const float*, float*, int,
-                   int, int, int64_t, int64_t, int64_t, int64_t,
+int mine_eav2_grid(int);
+void mine_eav2_fwd(const float*, const float*, const float*, float*, float*,
+                   int, int, int, int64_t, int64_t, int64_t, int64_t,
                    hipStream_t);
 void mine_eav2_bwd(const float*, const float*, const float*, float*, float*,
-                   const float*, float*, int, int, int, int64_t, int64_t,
-                   int64_t, int64_t, hipStream_t);
+                   float*, const float*, float*, int, int, int, int64_t,
+                   int64_t, int64_t, int64_t, hipStream_t);
+void mine_gather_pxpy_bwd(const float*, const int64_t*, float*, int, int, int,
+                          int64_t, hipStream_t);
 void mine_pack_gather(const void*, const int*, void*, int64_t, int, int,
                       hipStream_t);
 void mine_upsample2x_fwd(const void*, void*, int64_t, int64_t, int64_t,
@@ -127,7 +132,8 @@ void mine_bn_act_bwd_dx_bf16(const void*, const void*, const void*,
                              const float*, const float*, void*, void*, int64_t,
                              int, int, int, hipStream_t);
 void mine_ssim_set_window(const float*);
-void mine_ssim_fwd(const float*, const float*, float*, int, int, int,
+int mine_ssim_tiles(int, int);
+void mine_ssim_fwd(const float*, const float*, float*, float*, int, int, int,
                    hipStream_t);
 void mine_ssim_bwd(const float*, const float*, const float*, float*, float*,
                    float*, float*, int, int, int, hipStream_t);
@@ -232,8 +238,10 @@ std::vector<at::Tensor> tgt_composite_fwd(at::Tensor mpi, at::Tensor hinv,
 // mode 1 (default): gather redesign — interior pixels write plain
 // per-plane payloads, a per-src-tile gather kernel inverts the map
 // (hfwd required). mode 0: the round-1 all-atomic scatter (kept for
-// A/B tests and as a fallback).
-// workspace (trailing, default none = allocate here) is the mode-1
+// A/B tests and as a fallback). mode 2: order-fixed — every target pixel
+// emits its payload and tgt_collect_kernel pulls it into grad_mpi with
+// no float atomic (deterministic mode; hfwd required).
+// workspace (trailing, default none = allocate here) is the mode-1 / 2
 // payload buffer, same shape as mpi. Its contents on entry do not
 // matter: the backward kernel writes every entry before the gather
 // kernel reads it, so it is at::empty here and a test may hand in a
@@ -247,11 +255,16 @@ at::Tensor tgt_composite_bwd(at::Tensor mpi, at::Tensor hinv, at::Tensor hfwd,
   const int B = mpi.size(0), S = mpi.size(1), H = mpi.size(2), W = mpi.size(3);
   TORCH_CHECK((int64_t)H * W * 4 < (int64_t(1) << 31),
               "one plane must stay below 2^31 floats (32-bit tap offsets)");
-  auto grad_mpi = at::zeros_like(mpi);
+  TORCH_CHECK(mode >= 0 && mode <= 2, "tgt_composite_bwd: unknown mode");
+  // mode 2 (order-fixed): the collect pass stores every grad_mpi entry,
+  // so there is no zero fill; the payload is the same workspace
+  auto grad_mpi = mode == 2 ? at::empty_like(mpi) : at::zeros_like(mpi);
   at::Tensor payload;
   float* pay_ptr = nullptr;
-  if (mode == 1) {
-    TORCH_CHECK(hfwd.numel() == (int64_t)B * S * 9, "hfwd required in gather mode");
+  if (mode >= 1) {
+    CHECK_IN(hfwd);
+    TORCH_CHECK(hfwd.numel() == (int64_t)B * S * 9,
+                "hfwd required in gather and order-fixed mode");
     if (workspace.has_value()) {
       payload = *workspace;
       CHECK_IN(payload);
@@ -264,7 +277,7 @@ at::Tensor tgt_composite_bwd(at::Tensor mpi, at::Tensor hinv, at::Tensor hfwd,
     pay_ptr = payload.data_ptr<float>();
   }
   mine_tgt_composite_bwd(mpi.data_ptr<float>(), hinv.data_ptr<float>(),
-                         mode == 1 ? hfwd.data_ptr<float>() : nullptr,
+                         mode >= 1 ? hfwd.data_ptr<float>() : nullptr,
                          m.data_ptr<float>(), tvec.data_ptr<float>(),
                          depths.data_ptr<float>(), optr(g_rgb), optr(g_depth),
                          grad_mpi.data_ptr<float>(), pay_ptr, B, S, H, W,
@@ -272,36 +285,90 @@ at::Tensor tgt_composite_bwd(at::Tensor mpi, at::Tensor hinv, at::Tensor hfwd,
   return grad_mpi;
 }
 
+// collect pass of the order-fixed warp backward alone, on a caller's
+// payload (B,S,H,W,4): grad_mpi[b,s,q] = sum over the target pixels whose
+// bilinear taps hit source texel q, in raster order
+at::Tensor tgt_collect(at::Tensor payload, at::Tensor hinv, at::Tensor hfwd) {
+  CHECK_IN(payload); CHECK_IN(hinv); CHECK_IN(hfwd);
+  TORCH_CHECK(payload.dim() == 5 && payload.size(4) == 4,
+              "payload must be (B,S,H,W,4)");
+  const int B = payload.size(0), S = payload.size(1), H = payload.size(2),
+            W = payload.size(3);
+  TORCH_CHECK(B > 0 && S > 0 && S <= 65535 && B <= 65535 && H > 0 && W > 0);
+  TORCH_CHECK((int64_t)H * W * 4 < (int64_t(1) << 31),
+              "one plane must stay below 2^31 floats (32-bit tap offsets)");
+  TORCH_CHECK(hinv.numel() == (int64_t)B * S * 9 &&
+              hfwd.numel() == (int64_t)B * S * 9,
+              "hinv and hfwd must be (B,S,3,3)");
+  auto grad_mpi = at::empty_like(payload);
+  mine_tgt_collect(payload.data_ptr<float>(), hinv.data_ptr<float>(),
+                   hfwd.data_ptr<float>(), grad_mpi.data_ptr<float>(), B, S,
+                   H, W, stream());
+  return grad_mpi;
+}
+
 // --------------------------------------------------------------------------
 // general igemm conv (encoder/neck/base shapes; igemm_kernels.hip)
 
 // fused edge-aware smoothness v2 (loss_kernels.hip)
-at::Tensor eav2_fwd(at::Tensor disp, at::Tensor img, at::Tensor mean_d) {
+// det (trailing, default false): every block stores its partial into an
+// unfilled workspace row and one block per output sums the rows in index
+// order, instead of one atomic per block (loss_kernels.hip).
+at::Tensor eav2_fwd(at::Tensor disp, at::Tensor img, at::Tensor mean_d,
+                    bool det) {
   TORCH_CHECK(disp.is_cuda() && disp.is_contiguous() &&
               disp.scalar_type() == at::kFloat &&
               img.scalar_type() == at::kFloat);
   const int B = disp.size(0), H = disp.size(2), W = disp.size(3);
-  auto out = at::zeros({2}, disp.options());
+  auto out = det ? at::empty({2}, disp.options())
+                 : at::zeros({2}, disp.options());
+  at::Tensor ws;
+  if (det) ws = at::empty({2, B, mine_eav2_grid(H * W)}, disp.options());
   mine_eav2_fwd(disp.data_ptr<float>(), img.data_ptr<float>(),
-                mean_d.data_ptr<float>(), out.data_ptr<float>(), B, H, W,
+                mean_d.data_ptr<float>(), out.data_ptr<float>(),
+                det ? ws.data_ptr<float>() : nullptr, B, H, W,
                 img.stride(0), img.stride(1), img.stride(2), img.stride(3),
                 stream());
   return out;
 }
 
 at::Tensor eav2_bwd(at::Tensor disp, at::Tensor img, at::Tensor mean_d,
-                    at::Tensor gl) {
+                    at::Tensor gl, bool det) {
   const int B = disp.size(0), H = disp.size(2), W = disp.size(3);
   auto g_d = at::empty({B, 1, H, W}, disp.options());
-  auto Tb = at::zeros({B}, disp.options());
+  auto Tb = det ? at::empty({B}, disp.options())
+                : at::zeros({B}, disp.options());
+  at::Tensor ws;
+  if (det) ws = at::empty({B, mine_eav2_grid(H * W)}, disp.options());
   auto grad = at::empty_like(disp);
   mine_eav2_bwd(disp.data_ptr<float>(), img.data_ptr<float>(),
                 mean_d.data_ptr<float>(), g_d.data_ptr<float>(),
-                Tb.data_ptr<float>(), gl.data_ptr<float>(),
-                grad.data_ptr<float>(), B, H, W,
+                Tb.data_ptr<float>(), det ? ws.data_ptr<float>() : nullptr,
+                gl.data_ptr<float>(), grad.data_ptr<float>(), B, H, W,
                 img.stride(0), img.stride(1), img.stride(2), img.stride(3),
                 stream());
   return grad;
+}
+
+// Backward of the sparse-point gather without atomics: grad_out (B,C,N),
+// idx (B,N) int64 flat pixel indices in [0, HW) -> (B,C,HW). Points that
+// share a pixel are summed in point order by the first of them.
+at::Tensor gather_pxpy_bwd(at::Tensor grad_out, at::Tensor idx, int64_t HW) {
+  CHECK_IN(grad_out);
+  TORCH_CHECK(idx.is_cuda() && idx.is_contiguous() &&
+              idx.scalar_type() == at::kLong, "idx must be int64 on GPU");
+  TORCH_CHECK(grad_out.dim() == 3 && idx.dim() == 2 &&
+              idx.size(0) == grad_out.size(0) &&
+              idx.size(1) == grad_out.size(2), "grad_out (B,C,N), idx (B,N)");
+  const int64_t B = grad_out.size(0), C = grad_out.size(1),
+                N = grad_out.size(2);
+  TORCH_CHECK(HW > 0 && B * C * N < (int64_t(1) << 31));
+  auto grad_img = at::zeros({B, C, HW}, grad_out.options());
+  if (B * C * N > 0)
+    mine_gather_pxpy_bwd(grad_out.data_ptr<float>(), idx.data_ptr<int64_t>(),
+                         grad_img.data_ptr<float>(), (int)B, (int)C, (int)N,
+                         HW, stream());
+  return grad_img;
 }
 
 // one-launch fragment pack: gather through a device LUT (neg -> 0) into
@@ -882,15 +949,22 @@ void ensure_window() {
   g_window_set = true;
 }
 
-std::vector<at::Tensor> ssim_fwd(at::Tensor img1, at::Tensor img2) {
+// det (trailing, default false): per-block partials in an unfilled
+// workspace, summed in index order by one block (ssim_kernels.hip)
+std::vector<at::Tensor> ssim_fwd(at::Tensor img1, at::Tensor img2, bool det) {
   CHECK_IN(img1); CHECK_IN(img2);
   TORCH_CHECK(img1.dim() == 4 && img1.sizes() == img2.sizes());
   ensure_window();
   const int BC = img1.size(0) * img1.size(1);
   const int H = img1.size(2), W = img1.size(3);
-  auto sum = at::zeros({1}, img1.options());
+  auto sum = det ? at::empty({1}, img1.options())
+                 : at::zeros({1}, img1.options());
+  at::Tensor ws;
+  if (det)
+    ws = at::empty({(int64_t)BC * mine_ssim_tiles(H, W)}, img1.options());
   mine_ssim_fwd(img1.data_ptr<float>(), img2.data_ptr<float>(),
-                sum.data_ptr<float>(), BC, H, W, stream());
+                sum.data_ptr<float>(), det ? ws.data_ptr<float>() : nullptr,
+                BC, H, W, stream());
   return {(sum / (double)(BC * (int64_t)H * W)).squeeze(0)};
 }
 
@@ -925,10 +999,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("bg_inf"), pybind11::arg("alpha"),
           pybind11::arg("g_rgb"), pybind11::arg("g_depth"),
           pybind11::arg("mode"), pybind11::arg("workspace") = pybind11::none());
-  mod.def("ssim_fwd", &ssim_fwd);
+  mod.def("tgt_collect", &tgt_collect,
+          "collect pass of the order-fixed warp backward on a given payload",
+          pybind11::arg("payload"), pybind11::arg("hinv"),
+          pybind11::arg("hfwd"));
+  mod.def("ssim_fwd", &ssim_fwd, pybind11::arg("img1"), pybind11::arg("img2"),
+          pybind11::arg("det") = false);
   mod.def("ssim_bwd", &ssim_bwd);
-  mod.def("eav2_fwd", &eav2_fwd, "fused edge-aware smoothness v2 fwd");
-  mod.def("eav2_bwd", &eav2_bwd, "fused edge-aware smoothness v2 bwd");
+  mod.def("eav2_fwd", &eav2_fwd, "fused edge-aware smoothness v2 fwd",
+          pybind11::arg("disp"), pybind11::arg("img"),
+          pybind11::arg("mean_d"), pybind11::arg("det") = false);
+  mod.def("eav2_bwd", &eav2_bwd, "fused edge-aware smoothness v2 bwd",
+          pybind11::arg("disp"), pybind11::arg("img"),
+          pybind11::arg("mean_d"), pybind11::arg("gl"),
+          pybind11::arg("det") = false);
+  mod.def("gather_pxpy_bwd", &gather_pxpy_bwd,
+          "atomic-free backward of the sparse-point gather",
+          pybind11::arg("grad_out"), pybind11::arg("idx"),
+          pybind11::arg("HW"));
   namespace py = pybind11;
   mod.def("pack_gather", &pack_gather,
           "one-launch fragment pack through a device LUT", py::arg("w"),

@@ -41,11 +41,19 @@ __device__ __forceinline__ float img_gy(const float* img, int64_t b_off,
   return s * (1.0f / 3.0f);
 }
 
+// DET (deterministic mode), here and in eav2_bwd_gd_kernel: instead of
+// one atomicAdd per block, each block stores its (already scaled)
+// partial into a workspace row and det_rows_sum_kernel adds the rows in
+// an order fixed by their count — the scheme of the deterministic BN
+// finish. The scaling stays where it is, so the two modes differ by
+// summation order alone.
+template <bool DET>
 __global__ void __launch_bounds__(kBlock)
 eav2_fwd_kernel(const float* __restrict__ disp,  // (B,H,W)
                 const float* __restrict__ img,   // strided (B,3,H,W)
                 const float* __restrict__ mean_d,  // (B)
-                float* __restrict__ out,           // (2) pre-zeroed
+                // (2) pre-zeroed; DET: (2, B, gridDim.x) unfilled
+                float* __restrict__ out,
                 int B, int H, int W,
                 int64_t isb, int64_t isc, int64_t isy, int64_t isx) {
   const int b = blockIdx.y;
@@ -81,19 +89,46 @@ eav2_fwd_kernel(const float* __restrict__ disp,  // (B,H,W)
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    atomicAdd(&out[0], red[0][0] / ((float)B * H * (W - 1)));
-    atomicAdd(&out[1], red[1][0] / ((float)B * (H - 1) * W));
+    if (DET) {
+      const int64_t row = (int64_t)b * gridDim.x + blockIdx.x;
+      out[row] = red[0][0] / ((float)B * H * (W - 1));
+      out[(int64_t)B * gridDim.x + row] = red[1][0] / ((float)B * (H - 1) * W);
+    } else {
+      atomicAdd(&out[0], red[0][0] / ((float)B * H * (W - 1)));
+      atomicAdd(&out[1], red[1][0] / ((float)B * (H - 1) * W));
+    }
   }
+}
+
+// out[r] = sum of ws[r * n .. r * n + n): one block per output, thread t
+// adds entries t, t + kBlock, ... in ascending order, then a fixed LDS
+// tree. The order depends on n alone.
+__global__ void __launch_bounds__(kBlock)
+det_rows_sum_kernel(const float* __restrict__ ws, int n,
+                    float* __restrict__ out) {
+  __shared__ float red[kBlock];
+  const float* row = ws + (int64_t)blockIdx.x * n;
+  float s = 0.0f;
+  for (int i = threadIdx.x; i < n; i += kBlock) s += row[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int st = kBlock / 2; st > 0; st >>= 1) {
+    if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = red[0];
 }
 
 // pass 1: g_d[i] = dL/dd_i (gathered from the <=4 difference terms) and
 // the per-image dot T_b = sum_i g_d[i] * disp[i]
+template <bool DET>
 __global__ void __launch_bounds__(kBlock)
 eav2_bwd_gd_kernel(const float* __restrict__ disp,
                    const float* __restrict__ img,
                    const float* __restrict__ mean_d,
                    float* __restrict__ g_d,    // (B,H,W)
-                   float* __restrict__ Tb,     // (B) pre-zeroed
+                   // (B) pre-zeroed; DET: (B, gridDim.x) unfilled
+                   float* __restrict__ Tb,
                    int B, int H, int W,
                    int64_t isb, int64_t isc, int64_t isy, int64_t isx) {
   const int b = blockIdx.y;
@@ -147,7 +182,10 @@ eav2_bwd_gd_kernel(const float* __restrict__ disp,
     if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
     __syncthreads();
   }
-  if (threadIdx.x == 0) atomicAdd(&Tb[b], red[0]);
+  if (threadIdx.x == 0) {
+    if (DET) Tb[(int64_t)b * gridDim.x + blockIdx.x] = red[0];
+    else atomicAdd(&Tb[b], red[0]);
+  }
 }
 
 // pass 2: grad_disp = gl * (g_d - T_b / ((m+eps) * HW)) / (m+eps)
@@ -172,6 +210,35 @@ eav2_bwd_finish_kernel(const float* __restrict__ g_d,
   (void)disp;
 }
 
+// Backward of the sparse-point gather out[b,c,n] = img[b,c,idx[b,n]]
+// (deterministic mode) without atomics. Several points may share a
+// pixel; the FIRST of them in point order owns it and adds the upstream
+// gradients of all of them in point order, the others store nothing.
+// N is a few hundred, so the quadratic scan costs nothing. grad_img is
+// pre-zeroed (pixels no point lands on).
+__global__ void __launch_bounds__(kBlock)
+gather_pxpy_bwd_kernel(const float* __restrict__ g,       // (B,C,N)
+                       const int64_t* __restrict__ idx,   // (B,N)
+                       float* __restrict__ grad_img,      // (B,C,HW)
+                       int B, int C, int N, int64_t HW) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= B * C * N) return;
+  const int n = i % N;
+  const int bc = i / N;
+  const int64_t* ib = idx + (int64_t)(bc / C) * N;
+  const int64_t p = ib[n];
+  if (p < 0 || p >= HW) return;
+  for (int m = 0; m < n; ++m) {
+    if (ib[m] == p) return;  // an earlier point owns this pixel
+  }
+  const float* gr = g + (int64_t)bc * N;
+  float s = gr[n];
+  for (int m = n + 1; m < N; ++m) {
+    if (ib[m] == p) s += gr[m];
+  }
+  grad_img[(int64_t)bc * HW + p] = s;
+}
+
 inline int gx_of(int HW) {
   int g = (HW + kBlock - 1) / kBlock;
   return g < 1024 ? g : 1024;
@@ -181,24 +248,56 @@ inline int gx_of(int HW) {
 
 extern "C" {
 
+// grid.x of the eav2 launches: the row count of the deterministic
+// workspaces
+int mine_eav2_grid(int HW) { return gx_of(HW); }
+
+// ws == nullptr: atomics into the pre-zeroed out (2). Otherwise ws is an
+// unfilled (2, B, mine_eav2_grid) workspace and out needs no fill.
 void mine_eav2_fwd(const float* disp, const float* img, const float* mean_d,
-                   float* out, int B, int H, int W, int64_t isb, int64_t isc,
-                   int64_t isy, int64_t isx, hipStream_t stream) {
+                   float* out, float* ws, int B, int H, int W, int64_t isb,
+                   int64_t isc, int64_t isy, int64_t isx,
+                   hipStream_t stream) {
   dim3 grid(gx_of(H * W), B);
-  hipLaunchKernelGGL(eav2_fwd_kernel, grid, dim3(kBlock), 0, stream, disp,
-                     img, mean_d, out, B, H, W, isb, isc, isy, isx);
+  if (ws == nullptr) {
+    hipLaunchKernelGGL(eav2_fwd_kernel<false>, grid, dim3(kBlock), 0, stream,
+                       disp, img, mean_d, out, B, H, W, isb, isc, isy, isx);
+    return;
+  }
+  hipLaunchKernelGGL(eav2_fwd_kernel<true>, grid, dim3(kBlock), 0, stream,
+                     disp, img, mean_d, ws, B, H, W, isb, isc, isy, isx);
+  hipLaunchKernelGGL(det_rows_sum_kernel, dim3(2), dim3(kBlock), 0, stream,
+                     ws, B * (int)grid.x, out);
 }
 
+// ws == nullptr: atomics into the pre-zeroed Tb (B). Otherwise ws is an
+// unfilled (B, mine_eav2_grid) workspace and Tb needs no fill.
 void mine_eav2_bwd(const float* disp, const float* img, const float* mean_d,
-                   float* g_d, float* Tb, const float* gl, float* grad,
-                   int B, int H, int W, int64_t isb, int64_t isc,
+                   float* g_d, float* Tb, float* ws, const float* gl,
+                   float* grad, int B, int H, int W, int64_t isb, int64_t isc,
                    int64_t isy, int64_t isx, hipStream_t stream) {
   dim3 grid(gx_of(H * W), B);
-  hipLaunchKernelGGL(eav2_bwd_gd_kernel, grid, dim3(kBlock), 0, stream,
-                     disp, img, mean_d, g_d, Tb, B, H, W, isb, isc, isy,
-                     isx);
+  if (ws == nullptr) {
+    hipLaunchKernelGGL(eav2_bwd_gd_kernel<false>, grid, dim3(kBlock), 0,
+                       stream, disp, img, mean_d, g_d, Tb, B, H, W, isb, isc,
+                       isy, isx);
+  } else {
+    hipLaunchKernelGGL(eav2_bwd_gd_kernel<true>, grid, dim3(kBlock), 0,
+                       stream, disp, img, mean_d, g_d, ws, B, H, W, isb, isc,
+                       isy, isx);
+    hipLaunchKernelGGL(det_rows_sum_kernel, dim3(B), dim3(kBlock), 0, stream,
+                       ws, (int)grid.x, Tb);
+  }
   hipLaunchKernelGGL(eav2_bwd_finish_kernel, grid, dim3(kBlock), 0, stream,
                      g_d, disp, mean_d, Tb, gl, grad, B, H, W);
+}
+
+void mine_gather_pxpy_bwd(const float* g, const int64_t* idx, float* grad_img,
+                          int B, int C, int N, int64_t HW,
+                          hipStream_t stream) {
+  const int total = B * C * N;
+  hipLaunchKernelGGL(gather_pxpy_bwd_kernel, dim3((total + kBlock - 1) / kBlock),
+                     dim3(kBlock), 0, stream, g, idx, grad_img, B, C, N, HW);
 }
 
 }  // extern "C"

@@ -572,7 +572,15 @@ DEV TgtTerm tgt_plane_terms(float4 rgbs, float vz, float delta, float3 gR) {
 // dead-transmittance break. tgt_gather_kernel then inverts the
 // map per source tile. Decomposition proven against the scatter form
 // in tests/test_kernel_sim.py::test_warp_backward_gather_decomposition.
-template <bool BG_INF, bool GATHER, bool ALPHA = false>
+//
+// EMIT mode (the order-fixed backward, mode 2 of the launcher): EVERY
+// target pixel, border-clamped ones included, writes its per-plane
+// gradient into `payload` (zeros behind the dead-transmittance break),
+// nothing is scattered and grad_mpi is never touched. tgt_collect_kernel
+// then pulls the payload into grad_mpi in a fixed order.
+enum TgtBwdMode : int { kTgtScatter = 0, kTgtGather = 1, kTgtEmit = 2 };
+
+template <bool BG_INF, int MODE, bool ALPHA = false>
 __global__ void __launch_bounds__(kBlock)
 tgt_composite_bwd_kernel(const float* __restrict__ mpi,
                          const float* __restrict__ hinv,
@@ -581,9 +589,12 @@ tgt_composite_bwd_kernel(const float* __restrict__ mpi,
                          const float* __restrict__ depths,
                          const float* __restrict__ g_rgb,
                          const float* __restrict__ g_depth,
-                         float* __restrict__ grad_mpi,  // pre-zeroed
-                         float* __restrict__ payload,   // fully written (GATHER)
+                         float* __restrict__ grad_mpi,  // pre-zeroed; unused (EMIT)
+                         float* __restrict__ payload,   // fully written (GATHER, EMIT)
                          int B, int S, int H, int W) {
+  constexpr bool GATHER = MODE == kTgtGather;
+  constexpr bool EMIT = MODE == kTgtEmit;
+  constexpr bool PAYLOAD = GATHER || EMIT;
   __shared__ float s_geom[kMaxS * 9];
   __shared__ float s_depth[kMaxS];
   const int b = blockIdx.y;
@@ -598,7 +609,7 @@ tgt_composite_bwd_kernel(const float* __restrict__ mpi,
 
   const int HW = H * W;
   const float* mpi_b = mpi + (int64_t)b * S * HW * 4;
-  float* gm_b = grad_mpi + (int64_t)b * S * HW * 4;
+  float* gm_b = EMIT ? nullptr : grad_mpi + (int64_t)b * S * HW * 4;
   for (int pix = blockIdx.x * kBlock + threadIdx.x; pix < HW;
        pix += gridDim.x * kBlock) {
     const int y = pix / W;
@@ -651,7 +662,7 @@ tgt_composite_bwd_kernel(const float* __restrict__ mpi,
     // ---- pass B: emit gradients, bilinear scatter ----
     double prR = 0.0, prV = 0.0, prW = 0.0;
     Ad = 1.0;
-    float* pay_b = GATHER ? payload + (int64_t)b * S * HW * 4 : nullptr;
+    float* pay_b = PAYLOAD ? payload + (int64_t)b * S * HW * 4 : nullptr;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     cur = sample_plane(mpi_b, 0, HW, s_geom, s_depth[0], M, tv, x, y, W, H);
     int s = 0;
@@ -688,9 +699,11 @@ tgt_composite_bwd_kernel(const float* __restrict__ mpi,
       const float4 g = make_float4(w * gR.x, w * gR.y, w * gR.z, dsigma);
       // payload is NOT pre-zeroed: this thread writes every (s, pix)
       // entry it owns — g where the taps are interior, zeros where the
-      // pixel goes through the atomic border path instead
-      const bool interior = GATHER && uv_interior(cur.pu, cur.pv, W, H);
-      if (GATHER) {
+      // pixel goes through the atomic border path instead (EMIT has no
+      // such path: every pixel's g goes into the payload)
+      const bool interior =
+          EMIT || (GATHER && uv_interior(cur.pu, cur.pv, W, H));
+      if (PAYLOAD) {
         // per-component selects: a select between two float4 objects
         // goes through scratch
         *reinterpret_cast<float4*>(pay_b + (int64_t)s * HW * 4 +
@@ -698,7 +711,7 @@ tgt_composite_bwd_kernel(const float* __restrict__ mpi,
             make_float4(interior ? g.x : 0.f, interior ? g.y : 0.f,
                         interior ? g.z : 0.f, interior ? g.w : 0.f);
       }
-      if (!interior) {
+      if (!EMIT && !interior) {
         scatter4(gm_b + (int64_t)s * HW * 4,
                  make_tap(cur.pu, cur.pv, W, H), W, g);
       }
@@ -707,7 +720,7 @@ tgt_composite_bwd_kernel(const float* __restrict__ mpi,
       // grad_mpi is pre-zeroed; dead-transmittance tail scatters ~0
       if (Ad < 1e-14) break;
     }
-    if (GATHER) {  // ... and zeros for the planes behind the break
+    if (PAYLOAD) {  // ... and zeros for the planes behind the break
       for (int s2 = s + 1; s2 < S; ++s2) {
         *reinterpret_cast<float4*>(pay_b + (int64_t)s2 * HW * 4 +
                                    (unsigned)pix * 4u) = zero4;
@@ -931,6 +944,179 @@ tgt_gather_kernel(const float* __restrict__ payload,  // (B,S,H,W,4)
   }
 }
 
+
+// ---------------------------------------------------------------------------
+// Collect pass of the order-fixed tgt backward (mode 2): a pull kernel
+// with no float atomic, global or LDS. Each source texel (b, s, qy, qx)
+// has ONE owner thread, which sums the contributions of all target
+// pixels whose taps hit it — target pixels in raster order (y, then x),
+// tap kinds in scatter4's order — and writes grad_mpi with a plain
+// store, zeros included (grad_mpi needs no zero fill). The order is a
+// function of the shapes and the geometry alone.
+//
+// MEMBERSHIP is decided exactly as the scatter decides it: make_tap of
+// project_uv on the same hinv row (contraction rule); a tap contributes
+// if it equals (qx, qy) and its weight is non-zero. Nothing else
+// decides membership.
+//
+// The search WINDOW is only a bound and errs on the wide side. A pixel
+// can reach the texel only if its clamped (u, v) lies in
+// (qx-1, qx+1) x (qy-1, qy+1); for a ring texel (qx == 0, qx == W-1,
+// qy == 0, qy == H-1) the outward condition is dropped, which is where
+// the border-clamped pixels arrive (a strip for an edge texel, up to a
+// quadrant for a corner). Where hz keeps one sign s over a target row,
+// u > k is s * ((h0 - k h6) x + (h1 - k h7) y + (h2 - k h8)) > 0, linear
+// in x, so every condition cuts the row to a half-line and the row
+// holds one candidate interval. The fp32 (u, v) of project_uv differ
+// from the exact ones by a few ulp of the terms; every condition is
+// therefore relaxed by m = 1e-5 * (sum of the term magnitudes), more
+// than a hundred times that error, and the interval is widened by one
+// pixel on each side. A row on which hz is not safely of one sign, or a
+// plane with a non-finite entry, scans the whole row: slower, never
+// wrong (the rule of tgt_gather_kernel). Interior texels bound their
+// rows with the four hfwd-mapped corners of their tap halo, again as
+// the gather kernel does; ring texels visit every row, most of which
+// come out empty in closed form.
+// ---------------------------------------------------------------------------
+
+// One condition s*(a x + c) > 0 relaxed by m, applied to the inclusive
+// candidate interval [lo, hi] of a row (x in [0, W-1]); widened by one
+// pixel. Returns false if the row holds no candidate at all.
+DEV bool clip_row(float a, float c, float m, int W, int& lo, int& hi) {
+  const float tiny = m / (float)W;  // |a| x stays below m over the row
+  if (a > tiny) {          // x > xb
+    const float xb = (-m - c) / a;
+    lo = max(lo, (int)clampf(floorf(xb), -1.0f, (float)W));
+  } else if (a < -tiny) {  // x < xb
+    const float xb = (-m - c) / a;
+    hi = min(hi, (int)clampf(ceilf(xb), -1.0f, (float)W));
+  } else if (c <= -2.0f * m) {
+    return false;          // a x + c <= -m on the whole row
+  }
+  return lo <= hi;
+}
+
+DEV void collect_tap(float4& acc, float w, float4 g) {
+#pragma clang fp contract(off)
+  // the addends of scatter4: the product is rounded, then added
+  acc.x = acc.x + w * g.x;
+  acc.y = acc.y + w * g.y;
+  acc.z = acc.z + w * g.z;
+  acc.w = acc.w + w * g.w;
+}
+
+__global__ void __launch_bounds__(kBlock)
+tgt_collect_kernel(const float* __restrict__ payload,  // (B,S,H,W,4)
+                   const float* __restrict__ hinv,     // (B,S,3,3) tgt->src
+                   const float* __restrict__ hfwd,     // (B,S,3,3) src->tgt
+                   float* __restrict__ grad_mpi,       // (B,S,H,W,4), stored
+                   int B, int S, int H, int W) {
+  __shared__ float s_Hi[9];
+  __shared__ float s_Hf[9];
+  const int s = blockIdx.y;
+  const int b = blockIdx.z;
+  if (threadIdx.x < 9) {
+    s_Hi[threadIdx.x] = hinv[((int64_t)b * S + s) * 9 + threadIdx.x];
+    s_Hf[threadIdx.x] = hfwd[((int64_t)b * S + s) * 9 + threadIdx.x];
+  }
+  __syncthreads();
+
+  const float fW1 = (float)(W - 1), fH1 = (float)(H - 1);
+  // term magnitudes of hx, hy, hz over the image (the relaxation scale)
+  const float Tx = fabsf(s_Hi[0]) * fW1 + fabsf(s_Hi[1]) * fH1 + fabsf(s_Hi[2]);
+  const float Ty = fabsf(s_Hi[3]) * fW1 + fabsf(s_Hi[4]) * fH1 + fabsf(s_Hi[5]);
+  const float Tz = fabsf(s_Hi[6]) * fW1 + fabsf(s_Hi[7]) * fH1 + fabsf(s_Hi[8]);
+  const bool finite = isfinite(Tx + Ty + Tz);
+  const float mz = 1e-5f * Tz;
+
+  const int HW = H * W;
+  const float* pay = payload + ((int64_t)b * S + s) * HW * 4;
+  float* gm = grad_mpi + ((int64_t)b * S + s) * HW * 4;
+  for (int q = blockIdx.x * kBlock + threadIdx.x; q < HW;
+       q += gridDim.x * kBlock) {
+    const int qy = q / W;
+    const int qx = q - qy * W;
+    // which of the four conditions hold for this texel (ring: the
+    // outward one is dropped)
+    const bool c_ul = qx > 0, c_uh = qx < W - 1;
+    const bool c_vl = qy > 0, c_vh = qy < H - 1;
+    const float kul = (float)(qx - 1), kuh = (float)(qx + 1);
+    const float kvl = (float)(qy - 1), kvh = (float)(qy + 1);
+
+    // ---- rows: interior texels from the hfwd image of the tap halo ----
+    int ylo = 0, yhi = H - 1;
+    if (finite && c_ul && c_uh && c_vl && c_vh) {
+      const float cx[2] = {(float)qx - 1.25f, (float)qx + 1.25f};
+      const float cy[2] = {(float)qy - 1.25f, (float)qy + 1.25f};
+      float mny = 1e30f, mxy = -1e30f;
+      bool pos = true, neg = true, fin = true;
+#pragma unroll
+      for (int ci = 0; ci < 4; ++ci) {
+        const float x = cx[ci & 1], y = cy[ci >> 1];
+        const float pz = s_Hf[6] * x + s_Hf[7] * y + s_Hf[8];
+        const float py = (s_Hf[3] * x + s_Hf[4] * y + s_Hf[5]) / pz;
+        pos = pos && (pz > 1e-8f);
+        neg = neg && (pz < -1e-8f);
+        fin = fin && isfinite(py);
+        mny = fminf(mny, py);
+        mxy = fmaxf(mxy, py);
+      }
+      // one sign of the depth over the halo: its image is convex and the
+      // corners bound it
+      if ((pos || neg) && fin) {
+        ylo = (int)clampf(floorf(mny - 1.0f), 0.0f, fH1);
+        yhi = (int)clampf(ceilf(mxy + 1.0f), 0.0f, fH1);
+      }
+    }
+
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int y = ylo; y <= yhi; ++y) {
+      int lo = 0, hi = W - 1;
+      const float fy = (float)y;
+      const float hz0 = s_Hi[7] * fy + s_Hi[8];
+      const float hz1 = s_Hi[6] * fW1 + hz0;
+      float sg = 0.0f;  // sign of hz over the row, 0 = not safely one sign
+      if (finite) {
+        if (hz0 > mz && hz1 > mz) sg = 1.0f;
+        else if (hz0 < -mz && hz1 < -mz) sg = -1.0f;
+      }
+      if (sg != 0.0f) {
+        bool any = true;
+#define CLIP(COND, K, SGN, R0, R1, R2, T)                                   \
+        if (any && (COND)) {                                                \
+          const float a_ = (SGN) * sg * (s_Hi[R0] - (K) * s_Hi[6]);         \
+          const float c_ = (SGN) * sg * ((s_Hi[R1] - (K) * s_Hi[7]) * fy +  \
+                                         (s_Hi[R2] - (K) * s_Hi[8]));       \
+          const float m_ = 1e-5f * ((T) + (fabsf(K) + 1.0f) * Tz);          \
+          any = clip_row(a_, c_, m_, W, lo, hi);                            \
+        }
+        CLIP(c_ul, kul, 1.0f, 0, 1, 2, Tx)    // u > qx - 1
+        CLIP(c_uh, kuh, -1.0f, 0, 1, 2, Tx)   // u < qx + 1
+        CLIP(c_vl, kvl, 1.0f, 3, 4, 5, Ty)    // v > qy - 1
+        CLIP(c_vh, kvh, -1.0f, 3, 4, 5, Ty)   // v < qy + 1
+#undef CLIP
+        if (!any) continue;
+        lo = max(lo, 0);
+        hi = min(hi, W - 1);
+      }
+      for (int x = lo; x <= hi; ++x) {
+        const float2 uv = project_uv(s_Hi, x, y);
+        const TapRef t = make_tap(uv.x, uv.y, W, H);
+        if ((t.x0 != qx && t.x1 != qx) || (t.y0 != qy && t.y1 != qy)) continue;
+        const float4 g = *reinterpret_cast<const float4*>(
+            pay + (unsigned)(y * W + x) * 4u);
+        const float w00 = (1 - t.wx) * (1 - t.wy), w01 = t.wx * (1 - t.wy);
+        const float w10 = (1 - t.wx) * t.wy, w11 = t.wx * t.wy;
+        if (t.x0 == qx && t.y0 == qy && w00 != 0.0f) collect_tap(acc, w00, g);
+        if (t.x1 == qx && t.y0 == qy && w01 != 0.0f) collect_tap(acc, w01, g);
+        if (t.x0 == qx && t.y1 == qy && w10 != 0.0f) collect_tap(acc, w10, g);
+        if (t.x1 == qx && t.y1 == qy && w11 != 0.0f) collect_tap(acc, w11, g);
+      }
+    }
+    *reinterpret_cast<float4*>(gm + (unsigned)q * 4u) = acc;
+  }
+}
+
 inline int grid_x(int HW) {
   int g = (HW + kBlock - 1) / kBlock;
   return g < 4096 ? g : 4096;
@@ -1018,8 +1204,19 @@ void mine_tgt_composite_fwd(const float* mpi, const float* hinv,
   })
 }
 
+// collect pass alone: grad_mpi (no fill needed) = pull of `payload`
+void mine_tgt_collect(const float* payload, const float* hinv,
+                      const float* hfwd, float* grad_mpi, int B, int S, int H,
+                      int W, hipStream_t stream) {
+  dim3 grid(grid_x(H * W), S, B);
+  hipLaunchKernelGGL(tgt_collect_kernel, grid, dim3(kBlock), 0, stream,
+                     payload, hinv, hfwd, grad_mpi, B, S, H, W);
+}
+
 // mode 0: scatter everywhere (round-1 path); mode 1: gather redesign
-// (payload + hfwd required; grad_mpi pre-zeroed, payload need not be).
+// (payload + hfwd required; grad_mpi pre-zeroed, payload need not be);
+// mode 2: order-fixed emit + collect (payload + hfwd required; neither
+// buffer needs a fill, grad_mpi is stored by the collect pass alone).
 void mine_tgt_composite_bwd(const float* mpi, const float* hinv,
                             const float* hfwd, const float* m_rki,
                             const float* tvec, const float* depths,
@@ -1028,13 +1225,31 @@ void mine_tgt_composite_bwd(const float* mpi, const float* hinv,
                             int B, int S, int H, int W, int bg_inf, int mode,
                             int alpha, hipStream_t stream) {
   dim3 grid(grid_x(H * W), B);
-#define TGT_BWD_BODY(BGv, ALv)                                                if (mode == 1) {                                                              hipLaunchKernelGGL((tgt_composite_bwd_kernel<BGv, true, ALv>), grid,                           dim3(kBlock), 0, stream, mpi, hinv, m_rki, tvec,                            depths, g_rgb, g_depth, grad_mpi, payload,                                  B, S, H, W);                                             const int tiles_x = (W + GT - 1) / GT;                                      const int tiles_y = (H + GT - 1) / GT;                                      dim3 ggrid(tiles_x * tiles_y, S, B);                                        hipLaunchKernelGGL(tgt_gather_kernel, ggrid, dim3(kGBlock), 0, stream,                          payload, hinv, hfwd, grad_mpi, B, S, H, W, tiles_x);   } else {                                                                      hipLaunchKernelGGL((tgt_composite_bwd_kernel<BGv, false, ALv>), grid,                          dim3(kBlock), 0, stream, mpi, hinv, m_rki, tvec,                            depths, g_rgb, g_depth, grad_mpi, nullptr,                                  B, S, H, W);                                           }
+#define TGT_BWD_LAUNCH(BGv, MODEv, ALv, GM, PAY)                              \
+  hipLaunchKernelGGL((tgt_composite_bwd_kernel<BGv, MODEv, ALv>), grid,       \
+                     dim3(kBlock), 0, stream, mpi, hinv, m_rki, tvec,         \
+                     depths, g_rgb, g_depth, GM, PAY, B, S, H, W)
+#define TGT_BWD_BODY(BGv, ALv)                                                \
+  if (mode == 2) {                                                            \
+    TGT_BWD_LAUNCH(BGv, kTgtEmit, ALv, nullptr, payload);                     \
+    mine_tgt_collect(payload, hinv, hfwd, grad_mpi, B, S, H, W, stream);      \
+  } else if (mode == 1) {                                                     \
+    TGT_BWD_LAUNCH(BGv, kTgtGather, ALv, grad_mpi, payload);                  \
+    const int tiles_x = (W + GT - 1) / GT;                                    \
+    const int tiles_y = (H + GT - 1) / GT;                                    \
+    dim3 ggrid(tiles_x * tiles_y, S, B);                                      \
+    hipLaunchKernelGGL(tgt_gather_kernel, ggrid, dim3(kGBlock), 0, stream,    \
+                       payload, hinv, hfwd, grad_mpi, B, S, H, W, tiles_x);   \
+  } else {                                                                    \
+    TGT_BWD_LAUNCH(BGv, kTgtScatter, ALv, grad_mpi, nullptr);                 \
+  }
   if (alpha) {
     TGT_BWD_BODY(false, true)
     return;
   }
   DISPATCH_BOOL(bg_inf, BG, { TGT_BWD_BODY(BG, false) })
 #undef TGT_BWD_BODY
+#undef TGT_BWD_LAUNCH
 }
 
 }  // extern "C"

@@ -100,6 +100,11 @@ DEV Moments yblur(const Smem& sm, int ty, int tx) {
   return m;
 }
 
+// DET (deterministic mode): instead of one atomicAdd per block, each
+// block stores its partial into out_sum[bc * tiles + tile] (an unfilled
+// workspace) and ssim_det_finish_kernel sums the rows in an order fixed
+// by their count — the scheme of the deterministic BN finish.
+template <bool DET>
 __global__ void __launch_bounds__(NT)
 ssim_fwd_kernel(const float* __restrict__ img1, const float* __restrict__ img2,
                 float* __restrict__ out_sum, int BC, int H, int W) {
@@ -140,7 +145,28 @@ ssim_fwd_kernel(const float* __restrict__ img1, const float* __restrict__ img2,
     if (tid < step) red[tid] += red[tid + step];
     __syncthreads();
   }
-  if (tid == 0) atomicAdd(out_sum, red[0]);
+  if (tid == 0) {
+    if (DET) out_sum[(int64_t)bc * gridDim.x + tile] = red[0];
+    else atomicAdd(out_sum, red[0]);
+  }
+}
+
+// One block: thread t adds rows t, t + NT, ... in ascending order, then
+// the fixed LDS tree of the kernels above. The order depends on n alone.
+__global__ void __launch_bounds__(NT)
+ssim_det_finish_kernel(const float* __restrict__ ws, int64_t n,
+                       float* __restrict__ out) {
+  __shared__ float red[NT];
+  const int tid = threadIdx.x;
+  float s = 0.0f;
+  for (int64_t i = tid; i < n; i += NT) s += ws[i];
+  red[tid] = s;
+  __syncthreads();
+  for (int step = NT / 2; step > 0; step >>= 1) {
+    if (tid < step) red[tid] += red[tid + step];
+    __syncthreads();
+  }
+  if (tid == 0) out[0] = red[0];
 }
 
 __global__ void __launch_bounds__(NT)
@@ -263,11 +289,24 @@ void mine_ssim_set_window(const float* host_win11) {
   hipMemcpyToSymbol(HIP_SYMBOL(c_win), host_win11, 11 * sizeof(float));
 }
 
+int mine_ssim_tiles(int H, int W) {
+  return ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
+}
+
+// ws == nullptr: atomic sum into the pre-zeroed out_sum. Otherwise ws is
+// an unfilled (BC * mine_ssim_tiles) workspace and out_sum needs no fill.
 void mine_ssim_fwd(const float* img1, const float* img2, float* out_sum,
-                   int BC, int H, int W, hipStream_t stream) {
-  const int tiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
-  hipLaunchKernelGGL(ssim_fwd_kernel, dim3(tiles, BC), dim3(NT), 0, stream,
-                     img1, img2, out_sum, BC, H, W);
+                   float* ws, int BC, int H, int W, hipStream_t stream) {
+  const int tiles = mine_ssim_tiles(H, W);
+  if (ws == nullptr) {
+    hipLaunchKernelGGL(ssim_fwd_kernel<false>, dim3(tiles, BC), dim3(NT), 0,
+                       stream, img1, img2, out_sum, BC, H, W);
+    return;
+  }
+  hipLaunchKernelGGL(ssim_fwd_kernel<true>, dim3(tiles, BC), dim3(NT), 0,
+                     stream, img1, img2, ws, BC, H, W);
+  hipLaunchKernelGGL(ssim_det_finish_kernel, dim3(1), dim3(NT), 0, stream,
+                     ws, (int64_t)BC * tiles, out_sum);
 }
 
 void mine_ssim_bwd(const float* img1, const float* img2, const float* gscale,

@@ -21,9 +21,34 @@ _SOBEL_X = torch.tensor([[-1.0, 0.0, 1.0],
 _SOBEL_Y = _SOBEL_X.transpose(0, 1).contiguous()
 
 
+def _spatial_gradient_slices(img: torch.Tensor,
+                             normalized: bool = True) -> torch.Tensor:
+    """`spatial_gradient` from shifted slices of a replicate pad built
+    with `torch.cat`. Its backward is slicing and adding only; the
+    backward of `F.pad(mode="replicate")` on the GPU adds the border
+    copies with atomics (four addends at a corner), so it is not
+    repeatable. Same response as the conv form up to fp32 summation
+    order."""
+    H, W = img.shape[-2:]
+    x = torch.cat((img[..., :1], img, img[..., -1:]), dim=-1)
+    x = torch.cat((x[..., :1, :], x, x[..., -1:, :]), dim=-2)
+
+    def s(dy, dx):
+        return x[..., dy:dy + H, dx:dx + W]
+
+    gx = (s(0, 2) - s(0, 0)) + 2.0 * (s(1, 2) - s(1, 0)) + (s(2, 2) - s(2, 0))
+    gy = (s(2, 0) - s(0, 0)) + 2.0 * (s(2, 1) - s(0, 1)) + (s(2, 2) - s(0, 2))
+    out = torch.stack((gx, gy), dim=2)
+    return out * 0.125 if normalized else out
+
+
 def spatial_gradient(img: torch.Tensor, normalized: bool = True) -> torch.Tensor:
     """Sobel gradients with replicate padding: BxCxHxW -> BxCx2xHxW
     (dim 2 = [dx, dy]); kornia-0.3.0-compatible."""
+    if img.is_cuda and img.requires_grad:
+        from mine_amd.ops.backend import is_deterministic
+        if is_deterministic():
+            return _spatial_gradient_slices(img, normalized)
     B, C, H, W = img.shape
     kx = _SOBEL_X.to(device=img.device, dtype=img.dtype)
     ky = _SOBEL_Y.to(device=img.device, dtype=img.dtype)
@@ -65,10 +90,14 @@ class _EdgeAwareV2Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, img, disp):
-        from mine_amd.ops.backend import get_extension
+        from mine_amd.ops.backend import get_extension, is_deterministic
         ext = get_extension(required=True)
         mean_d = disp.detach().mean((1, 2, 3))
-        out = ext.eav2_fwd(disp, img, mean_d)
+        # deterministic mode: per-block partials summed in a fixed order
+        # (forward scalars, and the backward's per-image dot Tb); read
+        # once here and kept for the backward, as ops/bn.py does
+        ctx.det = is_deterministic()
+        out = ext.eav2_fwd(disp, img, mean_d, ctx.det)
         ctx.save_for_backward(img, disp, mean_d)
         return out[0] + out[1]
 
@@ -77,7 +106,8 @@ class _EdgeAwareV2Fn(torch.autograd.Function):
         from mine_amd.ops.backend import get_extension
         ext = get_extension(required=True)
         img, disp, mean_d = ctx.saved_tensors
-        grad = ext.eav2_bwd(disp, img, mean_d, gl.reshape(1).contiguous())
+        grad = ext.eav2_bwd(disp, img, mean_d, gl.reshape(1).contiguous(),
+                            ctx.det)
         return None, grad
 
 

@@ -30,7 +30,7 @@ from typing import Optional, Tuple
 import torch
 
 from mine_amd.ops import torch_ref as tr
-from mine_amd.ops.backend import get_extension
+from mine_amd.ops.backend import get_extension, is_deterministic
 
 _TGT_BWD_MODE = None
 
@@ -38,7 +38,8 @@ _TGT_BWD_MODE = None
 def tgt_bwd_mode() -> int:
     """1 (default) = gather-based warp backward (per-src-tile inversion,
     no interior atomics); 0 = the round-1 all-atomic bilinear scatter.
-    Override with MINE_TGT_BWD=scatter."""
+    Override with MINE_TGT_BWD=scatter. Deterministic mode runs mode 2
+    (order-fixed emit + collect) whatever this returns."""
     global _TGT_BWD_MODE
     if _TGT_BWD_MODE is None:
         import os
@@ -180,6 +181,9 @@ class _TgtCompositeFn(torch.autograd.Function):
         ctx.save_for_backward(mpi, hinv, m, tvec, depths)
         ctx.bg_inf = bool(bg_inf)
         ctx.alpha = bool(alpha)
+        # read once here (as ops/bn.py does): a graph built in
+        # deterministic mode keeps the order-fixed backward
+        ctx.det = is_deterministic()
         return rgb, depth, mask
 
     @staticmethod
@@ -187,10 +191,12 @@ class _TgtCompositeFn(torch.autograd.Function):
         mpi, hinv, m, tvec, depths = ctx.saved_tensors
         ext = get_extension(required=True)
         empty = torch.empty(0, device=mpi.device, dtype=torch.float32)
-        mode = tgt_bwd_mode()
-        if mode == 1:
-            # gather redesign: the per-src-tile inversion needs the
-            # forward (src -> tgt pixel) homographies
+        # mode 2 (order-fixed emit + collect, no float atomics) overrides
+        # MINE_TGT_BWD in deterministic mode
+        mode = 2 if ctx.det else tgt_bwd_mode()
+        if mode >= 1:
+            # gather / collect: inverting the map per source tile or texel
+            # needs the forward (src -> tgt pixel) homographies
             from mine_amd.utils.geometry import inverse_3x3
             with torch.no_grad():
                 B, S = hinv.shape[0], hinv.shape[1]

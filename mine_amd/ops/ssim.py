@@ -14,7 +14,7 @@ from typing import Dict, Tuple
 import torch
 import torch.nn.functional as F
 
-from mine_amd.ops.backend import get_extension
+from mine_amd.ops.backend import get_extension, is_deterministic
 
 _C1 = 0.01 ** 2
 _C2 = 0.03 ** 2
@@ -56,7 +56,9 @@ class _SsimFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img1, img2):
         ext = get_extension(required=True)
-        mean, = ext.ssim_fwd(img1, img2)
+        # deterministic mode: per-block partials summed in a fixed order
+        # instead of one atomic per block (the backward has no reduction)
+        mean, = ext.ssim_fwd(img1, img2, is_deterministic())
         ctx.save_for_backward(img1, img2)
         return mean
 

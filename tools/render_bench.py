@@ -4,7 +4,7 @@ four scales, as effective bandwidth.
 
     python tools/render_bench.py [--root OTHER_CHECKOUT] [--reps 9]
                                  [--scales 0,1,2,3] [--only {all,fwd,bwd}]
-                                 [--no-split]
+                                 [--no-split] [--mode {1,2}]
 
 B = 4, S = 64, fp32 MPI (B,S,H,W,4) at 256x384, 128x192, 64x96, 32x48.
 Seeded inputs: small camera motion, and sigma small enough that the
@@ -24,6 +24,10 @@ kernel 2N (read payload, write grad_mpi), fill N. The ceiling printed next
 to them is what the fused BN+activation forward kernel (one read + one
 write) reaches on a tensor of N bytes in the same process.
 
+--mode 2 times the order-fixed backward of deterministic mode instead:
+the emit instance of the backward kernel, `tgt_collect_kernel` in the
+gather kernel's place, and no fill at all.
+
 --root imports mine_amd from another built checkout, so two builds can be
 timed with the same scenes. --only and --scales narrow the run to a few
 dispatches for a counter collection.
@@ -36,6 +40,7 @@ ap.add_argument("--reps", type=int, default=9)
 ap.add_argument("--scales", default="0,1,2,3")
 ap.add_argument("--only", choices=("all", "fwd", "bwd"), default="all")
 ap.add_argument("--no-split", action="store_true")
+ap.add_argument("--mode", type=int, choices=(1, 2), default=1)
 args = ap.parse_args()
 sys.path.insert(0, args.root)
 import torch
@@ -48,7 +53,8 @@ B, S = 4, 64
 SCALES = [(256, 384), (128, 192), (64, 96), (32, 48)]
 ext = get_extension(required=True)
 HAS_WS = "workspace" in (ext.tgt_composite_bwd.__doc__ or "")
-N_FILLS = 1 if HAS_WS else 2
+N_FILLS = 0 if args.mode == 2 else (1 if HAS_WS else 2)
+PULL = "tgt_collect_kernel" if args.mode == 2 else "tgt_gather_kernel"
 
 
 def tm(fn, reps):
@@ -119,14 +125,15 @@ def kernel_split(fn, reps):
     per = {}
     for ev in p.events():
         if ev.device_type == torch.autograd.DeviceType.CUDA:
-            for key in ("tgt_composite_bwd_kernel", "tgt_gather_kernel"):
+            for key in ("tgt_composite_bwd_kernel", PULL):
                 if key in ev.name:
                     per.setdefault(key, []).append(ev.device_time / 1e3)
     return {k: sorted(v)[len(v) // 2] for k, v in per.items()}
 
 
 print(f"root {args.root}")
-print(f"binding takes workspace: {HAS_WS} -> {N_FILLS} zero fill(s) per call")
+print(f"mode {args.mode}; binding takes workspace: {HAS_WS} -> {N_FILLS} "
+      f"zero fill(s) per call")
 print(f"{'HxW':>9} {'N MB':>6} {'ceil':>5} | {'what':<14} {'ms':>7} {'TB/s':>5} "
       f"{'%ceil':>5}")
 tot = {}
@@ -144,16 +151,17 @@ for si in [int(v) for v in args.scales.split(",")]:
         if args.only in ("all", "bwd"):
             bwd = lambda: ext.tgt_composite_bwd(mpi, hinv, hfwd, m, tvec,
                                                 depths, False, False, g_rgb,
-                                                g_depth, 1)
+                                                g_depth, args.mode)
             t = tm(bwd, args.reps)
             rows.append(("bwd call", t, (4 + N_FILLS) * N))
-            tf = tm(lambda: torch.zeros_like(mpi), args.reps)
-            rows.append((f"fill x{N_FILLS}", N_FILLS * tf, N_FILLS * N))
+            if N_FILLS:
+                tf = tm(lambda: torch.zeros_like(mpi), args.reps)
+                rows.append((f"fill x{N_FILLS}", N_FILLS * tf, N_FILLS * N))
             if not args.no_split:
                 sp = kernel_split(bwd, args.reps)
                 rows.append(("bwd kernel", sp["tgt_composite_bwd_kernel"],
                              2 * N))
-                rows.append(("gather kernel", sp["tgt_gather_kernel"], 2 * N))
+                rows.append((PULL[4:].replace("_", " "), sp[PULL], 2 * N))
     for what, t, nbytes in rows:
         rate = nbytes / t / 1e9
         print(f"{H:>4}x{W:<4} {N / 1e6:6.1f} {ceil:5.2f} | {what:<14} {t:7.3f} "
