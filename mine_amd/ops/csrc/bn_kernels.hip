@@ -30,6 +30,8 @@
 #include <hip/hip_bf16.h>
 #include <cstdint>
 
+#include "launchers.h"
+
 namespace {
 
 constexpr int kBlock = 256;
@@ -995,77 +997,93 @@ void launch_bn_act_bwd_dx(const void* x, const void* res, const void* gy,
                      C, act);
 }
 
+// x = T(T(y_base + bias) + y_dec) and its (sum, sumsq); C % 8 == 0
+template <typename T, bool DET>
+void launch_bn_join_stats(const void* y_dec, const void* y_base,
+                          const void* bias, void* x, float* sums, int64_t M,
+                          int HW, int S, int C, int max_blocks,
+                          hipStream_t s) {
+  constexpr int V = 8;
+  const int Cv = C / V;
+  const int cgv = chan_group_v(Cv);
+  hipLaunchKernelGGL((bn_join_stats_vec_kernel<T, V, DET>),
+                     grid_reduce_v(M, Cv, cgv, max_blocks), dim3(kBlock), 0, s,
+                     reinterpret_cast<const T*>(y_dec),
+                     reinterpret_cast<const T*>(y_base),
+                     reinterpret_cast<const T*>(bias), reinterpret_cast<T*>(x),
+                     sums, M, HW, S, C, cgv);
+}
+
 }  // namespace
 
-#define EXPORT_BN(SUF, T)                                                      \
-  extern "C" void mine_bn_stats_##SUF(const void* x, float* sums, int64_t M,   \
-                                      int C, int max_blocks, int det,          \
-                                      hipStream_t s) {                         \
-    if (det) launch_bn_stats<T, true>(x, sums, M, C, max_blocks, s);           \
-    else launch_bn_stats<T, false>(x, sums, M, C, max_blocks, s);              \
-  }                                                                            \
-  extern "C" int mine_bn_reduce_grid_##SUF(int64_t M, int C, int max_blocks) { \
-    return reduce_grid_x<T>(M, C, max_blocks);                                 \
-  }                                                                            \
-  extern "C" void mine_bn_act_fwd_##SUF(                                       \
-      const void* x, const void* res, const float* mean, const float* invstd,  \
-      const float* gamma, const float* beta, void* y, int64_t M, int C,        \
-      int act, int max_blocks, hipStream_t s) {                                \
-    launch_bn_act_fwd<T>(x, res, mean, invstd, gamma, beta, y, M, C, act,      \
-                         max_blocks, s);                                       \
-  }                                                                            \
-  extern "C" void mine_bn_act_bwd_reduce_##SUF(                                \
-      const void* x, const void* res, const void* gy, const float* mean,       \
-      const float* invstd, const float* gamma, const float* beta, float* out,  \
-      int64_t M, int C, int act, int max_blocks, int det, hipStream_t s) {     \
-    if (det)                                                                   \
-      launch_bn_act_bwd_reduce<T, true>(x, res, gy, mean, invstd, gamma, beta, \
-                                        out, M, C, act, max_blocks, s);        \
-    else                                                                       \
-      launch_bn_act_bwd_reduce<T, false>(x, res, gy, mean, invstd, gamma,      \
-                                         beta, out, M, C, act, max_blocks, s); \
-  }                                                                            \
-  extern "C" void mine_bn_act_bwd_dx_##SUF(                                    \
-      const void* x, const void* res, const void* gy, const float* mean,       \
-      const float* invstd, const float* gamma, const float* beta,              \
-      const float* red, void* dx, void* dres, int64_t M, int C, int act,       \
-      int max_blocks, hipStream_t s) {                                         \
-    launch_bn_act_bwd_dx<T>(x, res, gy, mean, invstd, gamma, beta, red, dx,    \
-                            dres, M, C, act, max_blocks, s);                   \
-  }
+extern "C" int mine_bn_reduce_grid(int64_t M, int C, int max_blocks,
+                                   int elem) {
+  int grid = kNoKernel;
+  MINE_ELEM_SWITCH(elem, grid = reduce_grid_x<T>(M, C, max_blocks))
+  return grid;
+}
 
-EXPORT_BN(f32, float)
-EXPORT_BN(bf16, __hip_bfloat16)
-EXPORT_BN(f16, _Float16)
+extern "C" int mine_bn_stats(const void* x, float* sums, int64_t M, int C,
+                             int max_blocks, int det, int elem,
+                             hipStream_t s) {
+  MINE_ELEM_SWITCH(
+      elem, det ? launch_bn_stats<T, true>(x, sums, M, C, max_blocks, s)
+                : launch_bn_stats<T, false>(x, sums, M, C, max_blocks, s))
+  return kLaunched;
+}
 
-// x = T(T(y_base + bias) + y_dec) and its (sum, sumsq); C % 8 == 0
-#define EXPORT_BN_JOIN(SUF, T)                                                 \
-  extern "C" void mine_bn_join_stats_##SUF(                                    \
-      const void* y_dec, const void* y_base, const void* bias, void* x,        \
-      float* sums, int64_t M, int HW, int S, int C, int max_blocks, int det,   \
-      hipStream_t s) {                                                         \
-    constexpr int V = 8;                                                       \
-    const int Cv = C / V;                                                      \
-    const int cgv = chan_group_v(Cv);                                          \
-    const dim3 grid = grid_reduce_v(M, Cv, cgv, max_blocks);                   \
-    if (det)                                                                   \
-      hipLaunchKernelGGL((bn_join_stats_vec_kernel<T, V, true>), grid,         \
-                         dim3(kBlock), 0, s,                                   \
-                         reinterpret_cast<const T*>(y_dec),                    \
-                         reinterpret_cast<const T*>(y_base),                   \
-                         reinterpret_cast<const T*>(bias),                     \
-                         reinterpret_cast<T*>(x), sums, M, HW, S, C, cgv);     \
-    else                                                                       \
-      hipLaunchKernelGGL((bn_join_stats_vec_kernel<T, V, false>), grid,        \
-                         dim3(kBlock), 0, s,                                   \
-                         reinterpret_cast<const T*>(y_dec),                    \
-                         reinterpret_cast<const T*>(y_base),                   \
-                         reinterpret_cast<const T*>(bias),                     \
-                         reinterpret_cast<T*>(x), sums, M, HW, S, C, cgv);     \
-  }
+extern "C" int mine_bn_join_stats(const void* y_dec, const void* y_base,
+                                  const void* bias, void* x, float* sums,
+                                  int64_t M, int HW, int S, int C,
+                                  int max_blocks, int det, int elem,
+                                  hipStream_t s) {
+  MINE_ELEM_SWITCH16(
+      elem, det ? launch_bn_join_stats<T, true>(y_dec, y_base, bias, x, sums,
+                                                M, HW, S, C, max_blocks, s)
+                : launch_bn_join_stats<T, false>(y_dec, y_base, bias, x, sums,
+                                                 M, HW, S, C, max_blocks, s))
+  return kLaunched;
+}
 
-EXPORT_BN_JOIN(bf16, __hip_bfloat16)
-EXPORT_BN_JOIN(f16, _Float16)
+extern "C" int mine_bn_act_fwd(const void* x, const void* res,
+                               const float* mean, const float* invstd,
+                               const float* gamma, const float* beta, void* y,
+                               int64_t M, int C, int act, int max_blocks,
+                               int elem, hipStream_t s) {
+  MINE_ELEM_SWITCH(elem, launch_bn_act_fwd<T>(x, res, mean, invstd, gamma,
+                                              beta, y, M, C, act, max_blocks,
+                                              s))
+  return kLaunched;
+}
+
+extern "C" int mine_bn_act_bwd_reduce(const void* x, const void* res,
+                                      const void* gy, const float* mean,
+                                      const float* invstd, const float* gamma,
+                                      const float* beta, float* out, int64_t M,
+                                      int C, int act, int max_blocks, int det,
+                                      int elem, hipStream_t s) {
+  MINE_ELEM_SWITCH(
+      elem, det ? launch_bn_act_bwd_reduce<T, true>(x, res, gy, mean, invstd,
+                                                    gamma, beta, out, M, C,
+                                                    act, max_blocks, s)
+                : launch_bn_act_bwd_reduce<T, false>(x, res, gy, mean, invstd,
+                                                     gamma, beta, out, M, C,
+                                                     act, max_blocks, s))
+  return kLaunched;
+}
+
+extern "C" int mine_bn_act_bwd_dx(const void* x, const void* res,
+                                  const void* gy, const float* mean,
+                                  const float* invstd, const float* gamma,
+                                  const float* beta, const float* red,
+                                  void* dx, void* dres, int64_t M, int C,
+                                  int act, int max_blocks, int elem,
+                                  hipStream_t s) {
+  MINE_ELEM_SWITCH(elem, launch_bn_act_bwd_dx<T>(x, res, gy, mean, invstd,
+                                                 gamma, beta, red, dx, dres, M,
+                                                 C, act, max_blocks, s))
+  return kLaunched;
+}
 
 // deterministic finish over ws[G][2][C]: writes `out` (2,C) if given and
 // finalizes into mean/invstd (+ running stats) if given

@@ -56,6 +56,7 @@
 #include <cstdint>
 
 #include "elem16.h"
+#include "launchers.h"
 
 namespace {
 
@@ -353,9 +354,9 @@ int conv3x3_fwd_t(const void* x, const void* wp, const float* bias, void* out,
                                         H, W, K, k0, src_h, src_w, off, stream)
             : launch_cv<T, PAD_ZERO>(C / 8, cin4, nk, x, wp, bias, out, N, H,
                                      W, K, k0, src_h, src_w, off, stream);
-    if (!ok) return -1;
+    if (!ok) return kNoKernel;
   }
-  return 0;
+  return kLaunched;
 }
 
 }  // namespace
@@ -363,21 +364,19 @@ int conv3x3_fwd_t(const void* x, const void* wp, const float* bias, void* out,
 // C = logical input channels (multiple of 8, <= 64); c_mem = channels
 // per pixel in memory: C, or 4 with C == 8 in zero-embed mode. Output
 // channels beyond 64 run as further launches over the same input.
-// x, wp and out share one element type: bf16, or fp16 with is_f16.
-// Returns 0, or -1 when no kernel is instantiated for the shape.
+// x, wp and out share the element type `elem`, bf16 or fp16.
+// Returns kNoKernel when no kernel is instantiated for the shape or type.
 extern "C" int mine_conv3x3_fwd(const void* x, const void* wp,
                                 const float* bias, void* out, int N, int H,
                                 int W, int C, int c_mem, int K, int pad_mode,
-                                int src_h, int src_w, int off, int is_f16,
+                                int src_h, int src_w, int off, int elem,
                                 hipStream_t stream) {
-  if (C % 8 || C < 8 || C > 64 || K < 1) return -1;
-  if (c_mem != C && !(c_mem == 4 && C == 8)) return -1;
-  return is_f16 ? conv3x3_fwd_t<_Float16>(x, wp, bias, out, N, H, W, C, c_mem,
-                                          K, pad_mode, src_h, src_w, off,
-                                          stream)
-                : conv3x3_fwd_t<__hip_bfloat16>(x, wp, bias, out, N, H, W, C,
-                                                c_mem, K, pad_mode, src_h,
-                                                src_w, off, stream);
+  if (C % 8 || C < 8 || C > 64 || K < 1) return kNoKernel;
+  if (c_mem != C && !(c_mem == 4 && C == 8)) return kNoKernel;
+  MINE_ELEM_SWITCH16(elem, return conv3x3_fwd_t<T>(x, wp, bias, out, N, H, W,
+                                                   C, c_mem, K, pad_mode,
+                                                   src_h, src_w, off, stream))
+  return kNoKernel;
 }
 
 // Gather a (K,C,3,3) weight into MFMA fragment order in one launch:
@@ -396,32 +395,23 @@ conv3x3_pack_kernel(const TIN* __restrict__ w, const int64_t* __restrict__ lut,
 }
 
 template <typename TOUT>
-void pack_t(const void* w, int w_kind, const int64_t* lut, void* out,
-            int64_t n_out, int64_t n_w, hipStream_t stream) {
+int pack_t(const void* w, int w_elem, const int64_t* lut, void* out,
+           int64_t n_out, int64_t n_w, hipStream_t stream) {
   const dim3 grid((unsigned)((n_out + kBlock - 1) / kBlock));
-  TOUT* o = reinterpret_cast<TOUT*>(out);
-  if (w_kind == 1)
-    hipLaunchKernelGGL((conv3x3_pack_kernel<__hip_bfloat16, TOUT>), grid,
-                       dim3(kBlock), 0, stream,
-                       reinterpret_cast<const __hip_bfloat16*>(w), lut, o,
-                       n_out, n_w);
-  else if (w_kind == 2)
-    hipLaunchKernelGGL((conv3x3_pack_kernel<_Float16, TOUT>), grid,
-                       dim3(kBlock), 0, stream,
-                       reinterpret_cast<const _Float16*>(w), lut, o, n_out,
-                       n_w);
-  else
-    hipLaunchKernelGGL((conv3x3_pack_kernel<float, TOUT>), grid, dim3(kBlock),
-                       0, stream, reinterpret_cast<const float*>(w), lut, o,
-                       n_out, n_w);
+  MINE_ELEM_SWITCH(w_elem,
+                   hipLaunchKernelGGL((conv3x3_pack_kernel<T, TOUT>), grid,
+                                      dim3(kBlock), 0, stream,
+                                      reinterpret_cast<const T*>(w), lut,
+                                      reinterpret_cast<TOUT*>(out), n_out,
+                                      n_w))
+  return kLaunched;
 }
 }  // namespace
 
-// w_kind: 0 fp32, 1 bf16, 2 fp16; the output is bf16, or fp16 with out_f16
-extern "C" void mine_conv3x3_pack(const void* w, int w_kind,
-                                  const int64_t* lut, void* out, int out_f16,
-                                  int64_t n_out, int64_t n_w,
-                                  hipStream_t stream) {
-  if (out_f16) pack_t<_Float16>(w, w_kind, lut, out, n_out, n_w, stream);
-  else pack_t<__hip_bfloat16>(w, w_kind, lut, out, n_out, n_w, stream);
+extern "C" int mine_conv3x3_pack(const void* w, int w_elem, const int64_t* lut,
+                                 void* out, int out_elem, int64_t n_out,
+                                 int64_t n_w, hipStream_t stream) {
+  MINE_ELEM_SWITCH16(out_elem,
+                     return pack_t<T>(w, w_elem, lut, out, n_out, n_w, stream))
+  return kNoKernel;
 }

@@ -13,6 +13,8 @@
 #include <hip/hip_bf16.h>
 #include <cstdint>
 
+#include "launchers.h"
+
 namespace {
 
 constexpr int kBlock = 256;
@@ -75,34 +77,43 @@ inline int grid_for(int64_t n) {
   return (int)(g < 65535 ? g : 65535);
 }
 
+template <typename T>
+void head_fwd_t(const void* z, float* out, int64_t N, int alpha,
+                hipStream_t s) {
+  if (alpha)
+    hipLaunchKernelGGL((mpi_head_fwd_kernel<T, true>), dim3(grid_for(N)),
+                       dim3(kBlock), 0, s, reinterpret_cast<const T*>(z), out,
+                       N);
+  else
+    hipLaunchKernelGGL((mpi_head_fwd_kernel<T, false>), dim3(grid_for(N)),
+                       dim3(kBlock), 0, s, reinterpret_cast<const T*>(z), out,
+                       N);
+}
+
+template <typename T>
+void head_bwd_t(const void* z, const float* gout, void* gz, int64_t N,
+                int alpha, hipStream_t s) {
+  if (alpha)
+    hipLaunchKernelGGL((mpi_head_bwd_kernel<T, true>), dim3(grid_for(N)),
+                       dim3(kBlock), 0, s, reinterpret_cast<const T*>(z),
+                       gout, reinterpret_cast<T*>(gz), N);
+  else
+    hipLaunchKernelGGL((mpi_head_bwd_kernel<T, false>), dim3(grid_for(N)),
+                       dim3(kBlock), 0, s, reinterpret_cast<const T*>(z),
+                       gout, reinterpret_cast<T*>(gz), N);
+}
+
 }  // namespace
 
-#define EXPORT_HEAD(SUF, T)                                                    \
-  extern "C" void mine_mpi_head_fwd_##SUF(const void* z, float* out,           \
-                                          int64_t N, int alpha,                \
-                                          hipStream_t s) {                     \
-    if (alpha)                                                                 \
-      hipLaunchKernelGGL((mpi_head_fwd_kernel<T, true>), dim3(grid_for(N)),    \
-                         dim3(kBlock), 0, s,                                   \
-                         reinterpret_cast<const T*>(z), out, N);               \
-    else                                                                       \
-      hipLaunchKernelGGL((mpi_head_fwd_kernel<T, false>), dim3(grid_for(N)),   \
-                         dim3(kBlock), 0, s,                                   \
-                         reinterpret_cast<const T*>(z), out, N);               \
-  }                                                                            \
-  extern "C" void mine_mpi_head_bwd_##SUF(const void* z, const float* gout,    \
-                                          void* gz, int64_t N, int alpha,      \
-                                          hipStream_t s) {                     \
-    if (alpha)                                                                 \
-      hipLaunchKernelGGL((mpi_head_bwd_kernel<T, true>), dim3(grid_for(N)),    \
-                         dim3(kBlock), 0, s, reinterpret_cast<const T*>(z),    \
-                         gout, reinterpret_cast<T*>(gz), N);                   \
-    else                                                                       \
-      hipLaunchKernelGGL((mpi_head_bwd_kernel<T, false>), dim3(grid_for(N)),   \
-                         dim3(kBlock), 0, s, reinterpret_cast<const T*>(z),    \
-                         gout, reinterpret_cast<T*>(gz), N);                   \
-  }
+extern "C" int mine_mpi_head_fwd(const void* z, float* out, int64_t N,
+                                 int alpha, int elem, hipStream_t s) {
+  MINE_ELEM_SWITCH(elem, head_fwd_t<T>(z, out, N, alpha, s))
+  return kLaunched;
+}
 
-EXPORT_HEAD(f32, float)
-EXPORT_HEAD(bf16, __hip_bfloat16)
-EXPORT_HEAD(f16, _Float16)
+extern "C" int mine_mpi_head_bwd(const void* z, const float* gout, void* gz,
+                                 int64_t N, int alpha, int elem,
+                                 hipStream_t s) {
+  MINE_ELEM_SWITCH(elem, head_bwd_t<T>(z, gout, gz, N, alpha, s))
+  return kLaunched;
+}

@@ -34,6 +34,7 @@
 #include <cstdint>
 
 #include "elem16.h"
+#include "launchers.h"
 
 namespace {
 
@@ -367,32 +368,25 @@ pack_gather_kernel(const TIN* __restrict__ w, const int* __restrict__ lut,
 }
 
 template <typename TOUT>
-void pack_gather_t(const void* w, const int* lut, void* out, int64_t n,
-                   int w_kind, hipStream_t stream) {
+int pack_gather_t(const void* w, const int* lut, void* out, int64_t n,
+                  int w_elem, hipStream_t stream) {
   const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-  TOUT* o = reinterpret_cast<TOUT*>(out);
-  if (w_kind == 1)
-    hipLaunchKernelGGL((pack_gather_kernel<__hip_bfloat16, TOUT>), grid,
-                       dim3(kBlock), 0, stream,
-                       reinterpret_cast<const __hip_bfloat16*>(w), lut, o, n);
-  else if (w_kind == 2)
-    hipLaunchKernelGGL((pack_gather_kernel<_Float16, TOUT>), grid,
-                       dim3(kBlock), 0, stream,
-                       reinterpret_cast<const _Float16*>(w), lut, o, n);
-  else
-    hipLaunchKernelGGL((pack_gather_kernel<float, TOUT>), grid, dim3(kBlock),
-                       0, stream, reinterpret_cast<const float*>(w), lut, o,
-                       n);
+  MINE_ELEM_SWITCH(w_elem,
+                   hipLaunchKernelGGL((pack_gather_kernel<T, TOUT>), grid,
+                                      dim3(kBlock), 0, stream,
+                                      reinterpret_cast<const T*>(w), lut,
+                                      reinterpret_cast<TOUT*>(out), n))
+  return kLaunched;
 }
 
 }  // namespace
 
-// w_kind: 0 fp32, 1 bf16, 2 fp16; the output is bf16, or fp16 with out_f16
-extern "C" void mine_pack_gather(const void* w, const int* lut, void* out,
-                                 int64_t n, int w_kind, int out_f16,
-                                 hipStream_t stream) {
-  if (out_f16) pack_gather_t<_Float16>(w, lut, out, n, w_kind, stream);
-  else pack_gather_t<__hip_bfloat16>(w, lut, out, n, w_kind, stream);
+extern "C" int mine_pack_gather(const void* w, const int* lut, void* out,
+                                int64_t n, int w_elem, int out_elem,
+                                hipStream_t stream) {
+  MINE_ELEM_SWITCH16(out_elem,
+                     return pack_gather_t<T>(w, lut, out, n, w_elem, stream))
+  return kNoKernel;
 }
 
 // ---------------------------------------------------------------------------
@@ -462,19 +456,16 @@ void igemm_fwd_t(
 // splitz > 1 requires ws: pre-zeroed fp32 (M,K), or with det an
 // unfilled fp32 (splitz,M,K); the epilogue launch adds the bias (det: and
 // the slices, in ascending order) and casts into out. x, wp and out are
-// bf16, or fp16 with is_f16.
-extern "C" void mine_conv_igemm_fwd(
+// of type `elem`, bf16 or fp16.
+extern "C" int mine_conv_igemm_fwd(
     const void* x, const void* wp, const float* bias, void* out, float* ws,
     int64_t M, int P, int Q, int K, int Hs, int Ws, int C,
     int R, int S, int SA, int SB, int SD, int SE, int pad_mode, int splitz,
-    int det, int is_f16, hipStream_t stream) {
-  if (is_f16)
-    igemm_fwd_t<_Float16>(x, wp, bias, out, ws, M, P, Q, K, Hs, Ws, C, R, S,
-                          SA, SB, SD, SE, pad_mode, splitz, det, stream);
-  else
-    igemm_fwd_t<__hip_bfloat16>(x, wp, bias, out, ws, M, P, Q, K, Hs, Ws, C,
-                                R, S, SA, SB, SD, SE, pad_mode, splitz, det,
-                                stream);
+    int det, int elem, hipStream_t stream) {
+  MINE_ELEM_SWITCH16(elem, igemm_fwd_t<T>(x, wp, bias, out, ws, M, P, Q, K, Hs,
+                                          Ws, C, R, S, SA, SB, SD, SE,
+                                          pad_mode, splitz, det, stream))
+  return kLaunched;
 }
 
 // pixel slabs of the weight gradient (grid.x); the deterministic mode's
@@ -535,17 +526,15 @@ void igemm_wrw_t(
 
 // ws_det == nullptr: atomics into the pre-zeroed dw. Otherwise the
 // deterministic pair: tiles into ws_det (slabs,K,C,R,S), unfilled, then
-// the finishing kernel writes dw (unfilled too). x and gy are bf16, or
-// fp16 with is_f16.
-extern "C" void mine_conv_igemm_wrw(
+// the finishing kernel writes dw (unfilled too). x and gy are of type
+// `elem`, bf16 or fp16.
+extern "C" int mine_conv_igemm_wrw(
     const void* x, const void* gy, float* dw, float* ws_det,
     int64_t M, int P, int Q, int K, int Hs, int Ws, int C,
-    int R, int S, int SA, int SB, int SD, int SE, int pad_mode, int is_f16,
+    int R, int S, int SA, int SB, int SD, int SE, int pad_mode, int elem,
     hipStream_t stream) {
-  if (is_f16)
-    igemm_wrw_t<_Float16>(x, gy, dw, ws_det, M, P, Q, K, Hs, Ws, C, R, S, SA,
-                          SB, SD, SE, pad_mode, stream);
-  else
-    igemm_wrw_t<__hip_bfloat16>(x, gy, dw, ws_det, M, P, Q, K, Hs, Ws, C, R,
-                                S, SA, SB, SD, SE, pad_mode, stream);
+  MINE_ELEM_SWITCH16(elem, igemm_wrw_t<T>(x, gy, dw, ws_det, M, P, Q, K, Hs,
+                                          Ws, C, R, S, SA, SB, SD, SE,
+                                          pad_mode, stream))
+  return kLaunched;
 }

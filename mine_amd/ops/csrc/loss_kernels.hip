@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "launchers.h"
+
 namespace {
 
 constexpr int kBlock = 256;

@@ -19,6 +19,8 @@
 #include <hip/hip_bf16.h>
 #include <cstdint>
 
+#include "launchers.h"
+
 namespace {
 
 constexpr int kBlock = 256;
@@ -115,69 +117,56 @@ inline int pick_vec(int C) {
   return 1;
 }
 
-}  // namespace
-
-#define PAD_LAUNCH(KERN, T, TOTAL, ...)                                       \
+// launch KERN<T, V> over total / V vectors, V the widest that divides C
+#define PAD_VEC_DISPATCH(KERN, TOTAL)                                         \
   do {                                                                        \
     const int v = pick_vec<T>(C);                                             \
     const int64_t tv = (TOTAL) / v;                                           \
     if (v == 8)                                                               \
       hipLaunchKernelGGL((KERN<T, 8>), dim3(grid_for(tv)), dim3(kBlock), 0,   \
-                         stream, __VA_ARGS__);                                \
+                         stream, src, dst, N, H, W, C, pad);                  \
     else if (v == 4)                                                          \
       hipLaunchKernelGGL((KERN<T, 4>), dim3(grid_for(tv)), dim3(kBlock), 0,   \
-                         stream, __VA_ARGS__);                                \
+                         stream, src, dst, N, H, W, C, pad);                  \
     else if (v == 2)                                                          \
       hipLaunchKernelGGL((KERN<T, 2>), dim3(grid_for(tv)), dim3(kBlock), 0,   \
-                         stream, __VA_ARGS__);                                \
+                         stream, src, dst, N, H, W, C, pad);                  \
     else                                                                      \
       hipLaunchKernelGGL((KERN<T, 1>), dim3(grid_for(tv)), dim3(kBlock), 0,   \
-                         stream, __VA_ARGS__);                                \
+                         stream, src, dst, N, H, W, C, pad);                  \
   } while (0)
 
-extern "C" {
-
-void mine_reflect_pad_fwd_f32(const float* in, float* out, int N, int H,
-                              int W, int C, int pad, hipStream_t stream) {
-  PAD_LAUNCH(reflect_pad_fwd_kernel, float,
-             (int64_t)N * (H + 2 * pad) * (W + 2 * pad) * C,
-             in, out, N, H, W, C, pad);
+template <typename T>
+void pad_fwd_t(const void* in, void* out, int N, int H, int W, int C, int pad,
+               hipStream_t stream) {
+  const T* src = reinterpret_cast<const T*>(in);
+  T* dst = reinterpret_cast<T*>(out);
+  PAD_VEC_DISPATCH(reflect_pad_fwd_kernel,
+                   (int64_t)N * (H + 2 * pad) * (W + 2 * pad) * C);
 }
 
-void mine_reflect_pad_fwd_bf16(const void* in, void* out, int N, int H,
-                               int W, int C, int pad, hipStream_t stream) {
-  PAD_LAUNCH(reflect_pad_fwd_kernel, __hip_bfloat16,
-             (int64_t)N * (H + 2 * pad) * (W + 2 * pad) * C,
-             reinterpret_cast<const __hip_bfloat16*>(in),
-             reinterpret_cast<__hip_bfloat16*>(out), N, H, W, C, pad);
+template <typename T>
+void pad_bwd_t(const void* gout, void* gin, int N, int H, int W, int C,
+               int pad, hipStream_t stream) {
+  const T* src = reinterpret_cast<const T*>(gout);
+  T* dst = reinterpret_cast<T*>(gin);
+  PAD_VEC_DISPATCH(reflect_pad_bwd_kernel, (int64_t)N * H * W * C);
 }
 
-void mine_reflect_pad_fwd_f16(const void* in, void* out, int N, int H,
-                              int W, int C, int pad, hipStream_t stream) {
-  PAD_LAUNCH(reflect_pad_fwd_kernel, _Float16,
-             (int64_t)N * (H + 2 * pad) * (W + 2 * pad) * C,
-             reinterpret_cast<const _Float16*>(in),
-             reinterpret_cast<_Float16*>(out), N, H, W, C, pad);
+#undef PAD_VEC_DISPATCH
+
+}  // namespace
+
+extern "C" int mine_reflect_pad_fwd(const void* in, void* out, int N, int H,
+                                    int W, int C, int pad, int elem,
+                                    hipStream_t stream) {
+  MINE_ELEM_SWITCH(elem, pad_fwd_t<T>(in, out, N, H, W, C, pad, stream))
+  return kLaunched;
 }
 
-void mine_reflect_pad_bwd_f32(const float* gout, float* gin, int N, int H,
-                              int W, int C, int pad, hipStream_t stream) {
-  PAD_LAUNCH(reflect_pad_bwd_kernel, float, (int64_t)N * H * W * C,
-             gout, gin, N, H, W, C, pad);
+extern "C" int mine_reflect_pad_bwd(const void* gout, void* gin, int N, int H,
+                                    int W, int C, int pad, int elem,
+                                    hipStream_t stream) {
+  MINE_ELEM_SWITCH(elem, pad_bwd_t<T>(gout, gin, N, H, W, C, pad, stream))
+  return kLaunched;
 }
-
-void mine_reflect_pad_bwd_bf16(const void* gout, void* gin, int N, int H,
-                               int W, int C, int pad, hipStream_t stream) {
-  PAD_LAUNCH(reflect_pad_bwd_kernel, __hip_bfloat16, (int64_t)N * H * W * C,
-             reinterpret_cast<const __hip_bfloat16*>(gout),
-             reinterpret_cast<__hip_bfloat16*>(gin), N, H, W, C, pad);
-}
-
-void mine_reflect_pad_bwd_f16(const void* gout, void* gin, int N, int H,
-                              int W, int C, int pad, hipStream_t stream) {
-  PAD_LAUNCH(reflect_pad_bwd_kernel, _Float16, (int64_t)N * H * W * C,
-             reinterpret_cast<const _Float16*>(gout),
-             reinterpret_cast<_Float16*>(gin), N, H, W, C, pad);
-}
-
-}  // extern "C"

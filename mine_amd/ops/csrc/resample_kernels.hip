@@ -12,6 +12,8 @@
 #include <hip/hip_bf16.h>
 #include <cstdint>
 
+#include "launchers.h"
+
 namespace {
 
 constexpr int kBlock = 256;
@@ -119,29 +121,19 @@ void upsample_bwd_t(const void* gout, void* gin, int64_t N, int64_t H,
 
 }  // namespace
 
-extern "C" {
-
-// kind: 0 fp32 (C % 4 == 0), 1 bf16, 2 fp16 (C % 8 == 0)
-void mine_upsample2x_fwd(const void* in, void* out, int64_t N, int64_t H,
-                         int64_t W, int64_t C, int kind,
-                         hipStream_t stream) {
-  if (kind == 1)
-    upsample_fwd_t<__hip_bfloat16, 8>(in, out, N, H, W, C, stream);
-  else if (kind == 2)
-    upsample_fwd_t<_Float16, 8>(in, out, N, H, W, C, stream);
-  else
-    upsample_fwd_t<float, 4>(in, out, N, H, W, C, stream);
+// f32 moves 4 channels per thread, the 16-bit types 8
+extern "C" int mine_upsample2x_fwd(const void* in, void* out, int64_t N,
+                                   int64_t H, int64_t W, int64_t C, int elem,
+                                   hipStream_t stream) {
+  MINE_ELEM_SWITCH(elem, (upsample_fwd_t<T, 16 / (int)sizeof(T)>(
+                             in, out, N, H, W, C, stream)))
+  return kLaunched;
 }
 
-void mine_upsample2x_bwd(const void* gout, void* gin, int64_t N, int64_t H,
-                         int64_t W, int64_t C, int kind,
-                         hipStream_t stream) {
-  if (kind == 1)
-    upsample_bwd_t<__hip_bfloat16, 8>(gout, gin, N, H, W, C, stream);
-  else if (kind == 2)
-    upsample_bwd_t<_Float16, 8>(gout, gin, N, H, W, C, stream);
-  else
-    upsample_bwd_t<float, 4>(gout, gin, N, H, W, C, stream);
+extern "C" int mine_upsample2x_bwd(const void* gout, void* gin, int64_t N,
+                                   int64_t H, int64_t W, int64_t C, int elem,
+                                   hipStream_t stream) {
+  MINE_ELEM_SWITCH(elem, (upsample_bwd_t<T, 16 / (int)sizeof(T)>(
+                             gout, gin, N, H, W, C, stream)))
+  return kLaunched;
 }
-
-}  // extern "C"

@@ -20,6 +20,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "launchers.h"
+
 #define DEV __device__ __forceinline__
 
 namespace {

@@ -49,6 +49,7 @@
 #include <cstdint>
 
 #include "elem16.h"
+#include "launchers.h"
 
 namespace {
 
@@ -485,17 +486,16 @@ void wrw_launch_t(const short* xs, const short* gs, float* ws, int N, int H,
 }
 }  // namespace
 
-// x (N,H,W,C), gy (N,H,W,Kmem), both bf16 or (is_f16) both fp16 -> dw
+// x (N,H,W,C), gy (N,H,W,Kmem), both of type `elem` (bf16 or fp16) -> dw
 // (K,C,3,3) fp32 and, where db is not null, db (K) fp32. Kmem is 4 or a
 // multiple of 8 with Kmem >= K; ws comes from mine_conv3x3_wrw_plan.
-// Returns 0, -1 if there is no kernel for (C, Kmem), -2 if a launch
-// failed.
+// Returns kNoKernel if there is no kernel for (C, Kmem) or the type.
 extern "C" int mine_conv3x3_wrw(const void* x, const void* gy, float* ws,
                                 float* dw, float* db, int N, int H, int W,
-                                int C, int Kmem, int K, int slabs, int is_f16,
+                                int C, int Kmem, int K, int slabs, int elem,
                                 hipStream_t stream) {
-  if (C % 16 != 0 || C < 16 || C > 64) return -1;
-  if (Kmem != 4 && Kmem % 8 != 0) return -1;
+  if (C % 16 != 0 || C < 16 || C > 64) return kNoKernel;
+  if (Kmem != 4 && Kmem % 8 != 0) return kNoKernel;
   const int CT = C / 16, KT = kt_for(CT, Kmem);
   const bool k4 = Kmem == 4;
   const int nkb = ((Kmem + 15) / 16 + KT - 1) / KT;
@@ -503,16 +503,14 @@ extern "C" int mine_conv3x3_wrw(const void* x, const void* gy, float* ws,
   const short* xs = reinterpret_cast<const short*>(x);
   const short* gs = reinterpret_cast<const short*>(gy);
   const int wb = db != nullptr;
-  if (is_f16)
-    wrw_launch_t<_Float16>(xs, gs, ws, N, H, W, Kmem, CT, KT, k4, grid, slabs,
-                           wb, stream);
-  else
-    wrw_launch_t<__hip_bfloat16>(xs, gs, ws, N, H, W, Kmem, CT, KT, k4, grid,
-                                 slabs, wb, stream);
-  if (hipGetLastError() != hipSuccess) return -2;
+  MINE_ELEM_SWITCH16(elem, wrw_launch_t<T>(xs, gs, ws, N, H, W, Kmem, CT, KT,
+                                           k4, grid, slabs, wb, stream))
+  // a refused launch stays pending for the caller's status check; the
+  // finish would only sum an unwritten workspace
+  if (hipPeekAtLastError() != hipSuccess) return kLaunched;
   const int n_vec = nkb * (CT * KT * 9 + KT) * 64;
   hipLaunchKernelGGL(conv3x3_wrw_finish_kernel, dim3((n_vec + 15) / 16),
                      dim3(kBlock), 0, stream, ws, dw, db, slabs, nkb, CT, KT,
                      K, wb);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+  return kLaunched;
 }

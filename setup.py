@@ -31,6 +31,11 @@ ext = CUDAExtension(
         os.path.join(CSRC, "igemm_kernels.hip"),
         os.path.join(CSRC, "loss_kernels.hip"),
     ],
+    # editing a header rebuilds the extension
+    depends=[
+        os.path.join(CSRC, "launchers.h"),
+        os.path.join(CSRC, "elem16.h"),
+    ],
     extra_compile_args={
         "cxx": ["-O3"],
         "nvcc": ["-O3", "--offload-arch=gfx950"],
