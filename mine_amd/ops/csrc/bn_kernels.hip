@@ -11,17 +11,22 @@
 // (the ResNet bottleneck residual join, ref resnet bottleneck
 // out = relu(bn3(conv3) + identity)).
 //
-// Reductions: each workgroup owns one channel-slab; lanes stride the
-// N*H*W axis with C-strided loads (coalesced along C across lanes in
+// Every kernel is templated on V, the channels a thread owns: 16 bytes of
+// T (one 16-byte access per row) when C is a multiple of that, else 1.
+// All of them share one lane map (LaneMap below), and the tensors arrive
+// as void* because a kernel only ever views them as vectors of V elements.
+//
+// Reductions (bn_reduce): each workgroup owns one channel-slab; lanes
+// stride the N*H*W axis (coalesced along C across lanes in
 // channels_last), reduce through LDS, then one fp32 atomicAdd per block
 // into the output accumulator. ~1e-8-relative partial-sum error at the
 // flagship sizes; backward is the same shape.
 //
-// Deterministic mode (DET = true instantiations of the five reduction
+// Deterministic mode (DET = true instantiations of the three reduction
 // kernels): same lane map and grid, so every thread sums the same rows,
 // but no atomics. Each thread stores its partials to LDS at
 // [row-in-block][channel]; after the barrier one thread per channel adds
-// the kBlock/cg rows in ascending order and stores the block's (2, nc)
+// the kBlock/cgv rows in ascending order and stores the block's (2, nc)
 // result with plain stores into a workspace [gridDim.x][2][C].
 // bn_det_finish_kernel then adds the gridDim.x partials per channel in a
 // fixed order (see its comment) and optionally finalizes.
@@ -39,35 +44,8 @@ constexpr int kBlock = 256;
 enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_LRELU = 2, ACT_ELU = 3,
                  ACT_ADD_RELU = 4 };
 
-template <typename T> struct Vec;
-template <> struct Vec<float> { using t = float; };
-template <> struct Vec<__hip_bfloat16> { using t = __hip_bfloat16; };
-// fp16 is the compiler's native half: same bits as __half / at::Half, and
-// its float conversions (RNE, overflow to inf) survive
-// __HIP_NO_HALF_CONVERSIONS__
-template <> struct Vec<_Float16> { using t = _Float16; };
-
-__device__ __forceinline__ float act_fwd(int act, float z) {
-  switch (act) {
-    case ACT_RELU: return z > 0.0f ? z : 0.0f;
-    case ACT_LRELU: return z > 0.0f ? z : 0.1f * z;
-    case ACT_ELU: return z > 0.0f ? z : __expf(z) - 1.0f;
-    default: return z;
-  }
-}
-
-// derivative as a function of the PRE-activation z
-__device__ __forceinline__ float act_grad(int act, float z) {
-  switch (act) {
-    case ACT_RELU: case ACT_ADD_RELU: return z > 0.0f ? 1.0f : 0.0f;
-    case ACT_LRELU: return z > 0.0f ? 1.0f : 0.1f;
-    case ACT_ELU: return z > 0.0f ? 1.0f : __expf(z);
-    default: return 1.0f;
-  }
-}
-
-// Compile-time variants for the vectorized kernels: the host switches on
-// `act` once per launch, so the element loop carries no branch chain.
+// The activation is a template parameter: the host switches on `act`
+// once per launch, so the element loop carries no branch chain.
 template <int ACT>
 __device__ __forceinline__ float act_fwd_t(float z) {
   if constexpr (ACT == ACT_RELU || ACT == ACT_ADD_RELU)
@@ -80,6 +58,7 @@ __device__ __forceinline__ float act_fwd_t(float z) {
     return z;
 }
 
+// derivative as a function of the PRE-activation z
 template <int ACT>
 __device__ __forceinline__ float act_grad_t(float z) {
   if constexpr (ACT == ACT_RELU || ACT == ACT_ADD_RELU)
@@ -92,22 +71,71 @@ __device__ __forceinline__ float act_grad_t(float z) {
     return 1.0f;
 }
 
-// ---------------------------------------------------------------------------
-// stats: per-channel sum and sum-of-squares over the N*H*W axis
-// ---------------------------------------------------------------------------
+// V consecutive channels of one row. fp16 is the compiler's native half
+// (_Float16): same bits as __half / at::Half, and its float conversions
+// (RNE, overflow to inf) survive __HIP_NO_HALF_CONVERSIONS__.
+template <typename T, int V>
+struct alignas(sizeof(T) * V) BnVec {
+  T v[V];
+};
 
-// channel-group width: the smallest power of two >= min(C, 64), so
+// channel-group width: the smallest power of two >= min(Cv, 64), so
 // small-C layers (the decoder's C=16 blocks) keep every lane busy
 // instead of idling 3/4 of the block.
-inline __host__ __device__ int chan_group(int C) {
+inline __host__ __device__ int chan_group(int Cv) {
   int g = 1;
-  while (g < C && g < 64) g <<= 1;
+  while (g < Cv && g < 64) g <<= 1;
   return g;
 }
 
+// ---------------------------------------------------------------------------
+// Lane map shared by every kernel below: a thread owns ONE channel vector
+// (lane_cv = tid & (cgv-1), channel chunks of cgv vectors on blockIdx.y)
+// and walks rows m = row0, row0 + rstride, ... with
+// rstride = gridDim.x * (kBlock / cgv). Its per-channel parameters are
+// loaded once into registers before the row loop, so the loop body holds
+// only 16-byte data accesses and arithmetic — no per-element modulo, no
+// parameter loads. cgv is a power of two <= 64; a non-power-of-two Cv
+// (C=24 -> Cv=3) idles the lanes with lane_cv >= ncv.
+//
+// Row / Stride are the integer widths of row0 / rstride: 64-bit in the
+// elementwise kernels, which step a 64-bit offset by them; int in the
+// reductions (the join: 64-bit row0), whose rstride <= kMaxGridReduce *
+// kBlock.
+// ---------------------------------------------------------------------------
+template <typename Row, typename Stride>
+struct LaneMap {
+  int cgv, c0v, ncv, lane_cv;
+
+  __device__ __forceinline__ LaneMap(int Cv, int cgv_)
+      : cgv(cgv_),
+        c0v(blockIdx.y * cgv),
+        ncv(min(cgv, Cv - c0v)),
+        lane_cv(threadIdx.x & (cgv - 1)) {}
+
+  // the thread's channel vector, and whether it has one
+  __device__ __forceinline__ int col() const { return c0v + lane_cv; }
+  __device__ __forceinline__ bool active() const { return lane_cv < ncv; }
+
+  // Functions, not members: the elementwise kernels retire their idle
+  // lanes before this division, and with it ahead of that return the
+  // compiler spends 8-17 more registers on dx, one wave per SIMD.
+  __device__ __forceinline__ int rows_per_blk() const { return kBlock / cgv; }
+  __device__ __forceinline__ Row row0() const {
+    return (Row)blockIdx.x * rows_per_blk() + threadIdx.x / cgv;
+  }
+  __device__ __forceinline__ Stride rstride() const {
+    return (Stride)gridDim.x * rows_per_blk();
+  }
+};
+
+// ---------------------------------------------------------------------------
+// reductions: two per-channel sums over the N*H*W axis
+// ---------------------------------------------------------------------------
+
 // Deterministic block combine. The caller has stored its V partials at
 // s_a/s_b[threadIdx.x * V + j], which IS [row][channel] with rows of
-// `width` = cg*V floats (tid = row*cg + lane_c). Column i of row r sits
+// `width` = cgv*V floats (tid = row*cgv + lane_cv). Column i of row r sits
 // at r*width + i, so consecutive threads read consecutive banks. Rows are
 // added in ascending order; the result goes to ws[blockIdx.x][2][C] at
 // channel col0 + i.
@@ -126,54 +154,92 @@ __device__ __forceinline__ void det_block_flush(
   }
 }
 
-template <typename T, bool DET>
-__global__ void __launch_bounds__(kBlock)
-bn_stats_kernel(const T* __restrict__ x, float* __restrict__ sums,  // (2,C)
-                int64_t M, int C, int cg) {
-  // grid.x: slabs of the M axis; grid.y: channel chunks of cg
-  const int c0 = blockIdx.y * cg;
-  const int nc = min(cg, C - c0);
-  __shared__ float s_sum[DET ? kBlock : 64], s_sq[DET ? kBlock : 64];
+// The body of every reduction kernel. row_loop(lm, a, b) adds the
+// thread's rows into its V partials of each sum; the block's partials are
+// then combined through LDS into out, (2,C): LDS atomics and one global
+// atomicAdd per channel, or with DET in fixed order into the workspace
+// out[gridDim.x][2][C].
+template <int V, bool DET, typename Row, typename RowLoop>
+__device__ __forceinline__ void bn_reduce(int C, int cgv,
+                                          float* __restrict__ out,
+                                          RowLoop&& row_loop) {
+  const LaneMap<Row, int> lm(C / V, cgv);
+  __shared__ float s_a[(DET ? kBlock : 64) * V], s_b[(DET ? kBlock : 64) * V];
   if constexpr (!DET) {
-    for (int i = threadIdx.x; i < cg; i += kBlock) {
-      s_sum[i] = 0.0f;
-      s_sq[i] = 0.0f;
+    for (int i = threadIdx.x; i < cgv * V; i += kBlock) {
+      s_a[i] = 0.0f;
+      s_b[i] = 0.0f;
     }
     __syncthreads();
   }
-
-  const int lane_c = threadIdx.x & (cg - 1);
-  const int rows_per_blk = kBlock / cg;
-  const int row0 = blockIdx.x * rows_per_blk + threadIdx.x / cg;
-  const int rstride = gridDim.x * rows_per_blk;
-  float lsum = 0.0f, lsq = 0.0f;
-  if (lane_c < nc) {
-    const int c = c0 + lane_c;
-    for (int64_t m = row0; m < M; m += rstride) {
-      const float v = (float)x[m * C + c];
-      lsum += v;
-      lsq += v * v;
-    }
-    if constexpr (DET) {
-      s_sum[threadIdx.x] = lsum;
-      s_sq[threadIdx.x] = lsq;
-    } else {
-      atomicAdd(&s_sum[lane_c], lsum);
-      atomicAdd(&s_sq[lane_c], lsq);
+  if (lm.active()) {
+    float a[V], b[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) a[j] = b[j] = 0.0f;
+    row_loop(lm, a, b);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      if constexpr (DET) {
+        s_a[threadIdx.x * V + j] = a[j];
+        s_b[threadIdx.x * V + j] = b[j];
+      } else {
+        atomicAdd(&s_a[lm.lane_cv * V + j], a[j]);
+        atomicAdd(&s_b[lm.lane_cv * V + j], b[j]);
+      }
     }
   }
   __syncthreads();
   if constexpr (DET) {
-    det_block_flush(s_sum, s_sq, cg, rows_per_blk, nc, sums, C, c0);
-    return;
-  }
-  for (int i = threadIdx.x; i < nc; i += kBlock) {
-    atomicAdd(&sums[c0 + i], s_sum[i]);
-    atomicAdd(&sums[C + c0 + i], s_sq[i]);
+    det_block_flush(s_a, s_b, cgv * V, lm.rows_per_blk(), lm.ncv * V, out, C,
+                    lm.c0v * V);
+  } else {
+    for (int i = threadIdx.x; i < lm.ncv * V; i += kBlock) {
+      atomicAdd(&out[lm.c0v * V + i], s_a[i]);
+      atomicAdd(&out[C + lm.c0v * V + i], s_b[i]);
+    }
   }
 }
 
-// finalize: mean/invstd from sums; update running stats
+// stats: per-channel sum and sum-of-squares
+template <typename T, int V, bool DET>
+__global__ void __launch_bounds__(kBlock)
+bn_stats_vec_kernel(const void* __restrict__ x, float* __restrict__ sums,
+                    int64_t M, int C, int cgv) {
+  using Vec = BnVec<T, V>;
+  bn_reduce<V, DET, int>(
+      C, cgv, sums, [&](const auto& lm, float (&acc)[V], float (&asq)[V]) {
+        const int Cv = C / V;
+        const Vec* xv = static_cast<const Vec*>(x);
+        const int rstride = lm.rstride();
+        for (int64_t m = lm.row0(); m < M; m += rstride) {
+          const Vec val = xv[m * Cv + lm.col()];
+#pragma unroll
+          for (int j = 0; j < V; ++j) {
+            const float f = (float)val.v[j];
+            acc[j] += f;
+            asq[j] += f * f;
+          }
+        }
+      });
+}
+
+// mean/invstd of one channel from its sums; updates the running stats
+__device__ __forceinline__ void bn_finalize_channel(
+    float sum, float sumsq, int c, float* __restrict__ mean,
+    float* __restrict__ invstd, float* __restrict__ running_mean,
+    float* __restrict__ running_var, int64_t M, float eps, float momentum) {
+  const float mu = sum / (float)M;
+  float var = sumsq / (float)M - mu * mu;
+  var = var > 0.0f ? var : 0.0f;
+  mean[c] = mu;
+  invstd[c] = rsqrtf(var + eps);
+  if (running_mean) {
+    running_mean[c] += momentum * (mu - running_mean[c]);
+    const float unbiased = M > 1 ? var * (float)M / (float)(M - 1) : var;
+    running_var[c] += momentum * (unbiased - running_var[c]);
+  }
+}
+
 __global__ void bn_finalize_kernel(const float* __restrict__ sums,
                                    float* __restrict__ mean,
                                    float* __restrict__ invstd,
@@ -183,16 +249,8 @@ __global__ void bn_finalize_kernel(const float* __restrict__ sums,
                                    float momentum) {
   const int c = blockIdx.x * kBlock + threadIdx.x;
   if (c >= C) return;
-  const float mu = sums[c] / (float)M;
-  float var = sums[C + c] / (float)M - mu * mu;
-  var = var > 0.0f ? var : 0.0f;
-  mean[c] = mu;
-  invstd[c] = rsqrtf(var + eps);
-  if (running_mean) {
-    running_mean[c] += momentum * (mu - running_mean[c]);
-    const float unbiased = M > 1 ? var * (float)M / (float)(M - 1) : var;
-    running_var[c] += momentum * (unbiased - running_var[c]);
-  }
+  bn_finalize_channel(sums[c], sums[C + c], c, mean, invstd, running_mean,
+                      running_var, M, eps, momentum);
 }
 
 // Deterministic finish: adds the G per-block partials ws[g][2][C] of each
@@ -206,7 +264,7 @@ __global__ void bn_finalize_kernel(const float* __restrict__ sums,
 //   level 2: one thread per channel adds the np lane partials in
 //            ascending p.
 // Then it writes the (2, C) sums to `out` (bn_sums, bn_join_stats,
-// bn_act_bwd_reduce) and/or, when `mean` is given, finalizes exactly as
+// bn_act_bwd_reduce) and/or, when `mean` is given, finalizes as
 // bn_finalize_kernel does (bn_stats) — so the mode adds no launch. A
 // separate launch after the reduction: no device-wide fence, no
 // last-block-to-arrive.
@@ -258,227 +316,125 @@ bn_det_finish_kernel(const float* __restrict__ ws, int G, int C, int cw,
     out[c] = ta;
     out[C + c] = tb;
   }
-  if (mean) {
-    const float mu = ta / (float)M;
-    float var = tb / (float)M - mu * mu;
-    var = var > 0.0f ? var : 0.0f;
-    mean[c] = mu;
-    invstd[c] = rsqrtf(var + eps);
-    if (running_mean) {
-      running_mean[c] += momentum * (mu - running_mean[c]);
-      const float unbiased = M > 1 ? var * (float)M / (float)(M - 1) : var;
-      running_var[c] += momentum * (unbiased - running_var[c]);
-    }
-  }
+  if (mean)
+    bn_finalize_channel(ta, tb, c, mean, invstd, running_mean, running_var, M,
+                        eps, momentum);
 }
 
-// ---------------------------------------------------------------------------
-// normalize + activation (and the optional residual add)
-// ---------------------------------------------------------------------------
-
-template <typename T>
-__global__ void __launch_bounds__(kBlock)
-bn_act_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res,
-                  const float* __restrict__ mean,
-                  const float* __restrict__ invstd,
-                  const float* __restrict__ gamma,
-                  const float* __restrict__ beta, T* __restrict__ y,
-                  int64_t M, int C, int act) {
-  const int64_t total = M * C;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total;
-       i += (int64_t)gridDim.x * kBlock) {
-    const int c = (int)(i % C);
-    float z = ((float)x[i] - mean[c]) * invstd[c] * gamma[c] + beta[c];
-    if (act == ACT_ADD_RELU) {
-      z += (float)res[i];
-      y[i] = (T)(z > 0.0f ? z : 0.0f);
-    } else {
-      y[i] = (T)act_fwd(act, z);
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
 // backward reduction: dbeta = sum g', dgamma = sum g' * xhat
 //   where g' = gy * act'(z), z recomputed from x
-// ---------------------------------------------------------------------------
-
-template <typename T, bool DET>
+template <typename T, int V, int ACT, bool DET>
 __global__ void __launch_bounds__(kBlock)
-bn_act_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ res,
-                         const T* __restrict__ gy,
-                         const float* __restrict__ mean,
-                         const float* __restrict__ invstd,
-                         const float* __restrict__ gamma,
-                         const float* __restrict__ beta,
-                         float* __restrict__ out,  // (2,C): dbeta, dgamma
-                         int64_t M, int C, int act, int cg) {
-  const int c0 = blockIdx.y * cg;
-  const int nc = min(cg, C - c0);
-  __shared__ float s_db[DET ? kBlock : 64], s_dg[DET ? kBlock : 64];
-  if constexpr (!DET) {
-    for (int i = threadIdx.x; i < cg; i += kBlock) {
-      s_db[i] = 0.0f;
-      s_dg[i] = 0.0f;
-    }
-    __syncthreads();
-  }
-  const int lane_c = threadIdx.x & (cg - 1);
-  const int rows_per_blk = kBlock / cg;
-  const int row0 = blockIdx.x * rows_per_blk + threadIdx.x / cg;
-  const int rstride = gridDim.x * rows_per_blk;
-  if (lane_c < nc) {
-    const int c = c0 + lane_c;
-    const float mu = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
-    float db = 0.0f, dg = 0.0f;
-    for (int64_t m = row0; m < M; m += rstride) {
-      const float xh = ((float)x[m * C + c] - mu) * is;
-      float z = xh * ga + be;
-      if (act == ACT_ADD_RELU) z += (float)res[m * C + c];
-      const float g = (float)gy[m * C + c] * act_grad(act, z);
-      db += g;
-      dg += g * xh;
-    }
-    if constexpr (DET) {
-      s_db[threadIdx.x] = db;
-      s_dg[threadIdx.x] = dg;
-    } else {
-      atomicAdd(&s_db[lane_c], db);
-      atomicAdd(&s_dg[lane_c], dg);
-    }
-  }
-  __syncthreads();
-  if constexpr (DET) {
-    det_block_flush(s_db, s_dg, cg, rows_per_blk, nc, out, C, c0);
-    return;
-  }
-  for (int i = threadIdx.x; i < nc; i += kBlock) {
-    atomicAdd(&out[c0 + i], s_db[i]);
-    atomicAdd(&out[C + c0 + i], s_dg[i]);
-  }
+bn_act_bwd_reduce_vec_kernel(const void* __restrict__ x,
+                             const void* __restrict__ res,
+                             const void* __restrict__ gy,
+                             const float* __restrict__ mean,
+                             const float* __restrict__ invstd,
+                             const float* __restrict__ gamma,
+                             const float* __restrict__ beta,
+                             float* __restrict__ out,  // (2,C)
+                             int64_t M, int C, int cgv) {
+  using Vec = BnVec<T, V>;
+  bn_reduce<V, DET, int>(
+      C, cgv, out, [&](const auto& lm, float (&db)[V], float (&dg)[V]) {
+        const int Cv = C / V;
+        const int cb = lm.col() * V;
+        float mu[V], is[V], ga[V], be[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          mu[j] = mean[cb + j];
+          is[j] = invstd[cb + j];
+          ga[j] = gamma[cb + j];
+          be[j] = beta[cb + j];
+        }
+        const Vec* xv = static_cast<const Vec*>(x);
+        const Vec* gv = static_cast<const Vec*>(gy);
+        const Vec* rv = static_cast<const Vec*>(res);
+        const int rstride = lm.rstride();
+        for (int64_t m = lm.row0(); m < M; m += rstride) {
+          const int64_t off = m * Cv + lm.col();
+          const Vec xval = xv[off];
+          const Vec gval = gv[off];
+          Vec rval;
+          if constexpr (ACT == ACT_ADD_RELU) rval = rv[off];
+#pragma unroll
+          for (int j = 0; j < V; ++j) {
+            const float xh = ((float)xval.v[j] - mu[j]) * is[j];
+            float z = xh * ga[j] + be[j];
+            if constexpr (ACT == ACT_ADD_RELU) z += (float)rval.v[j];
+            const float g = (float)gval.v[j] * act_grad_t<ACT>(z);
+            db[j] += g;
+            dg[j] += g * xh;
+          }
+        }
+      });
 }
-
-// dx = gamma*invstd * (g' - (dbeta + xhat*dgamma)/M); optional dres = g'
-template <typename T>
-__global__ void __launch_bounds__(kBlock)
-bn_act_bwd_dx_kernel(const T* __restrict__ x, const T* __restrict__ res,
-                     const T* __restrict__ gy,
-                     const float* __restrict__ mean,
-                     const float* __restrict__ invstd,
-                     const float* __restrict__ gamma,
-                     const float* __restrict__ beta,
-                     const float* __restrict__ red,  // (2,C)
-                     T* __restrict__ dx, T* __restrict__ dres,
-                     int64_t M, int C, int act) {
-  const float invM = 1.0f / (float)M;
-  const int64_t total = M * C;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total;
-       i += (int64_t)gridDim.x * kBlock) {
-    const int c = (int)(i % C);
-    const float mu = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
-    const float xh = ((float)x[i] - mu) * is;
-    float z = xh * ga + be;
-    if (act == ACT_ADD_RELU) z += (float)res[i];
-    const float g = (float)gy[i] * act_grad(act, z);
-    if (act == ACT_ADD_RELU) dres[i] = (T)g;
-    dx[i] = (T)(ga * is * (g - (red[c] + xh * red[C + c]) * invM));
-  }
-}
-
-// eval-mode: normalize with given (running) stats + activation
-// (same bn_act_fwd_kernel with mean/invstd precomputed on host side)
-
-inline int grid_elems(int64_t total) {
-  int64_t g = (total + kBlock - 1) / kBlock;
-  return (int)(g < 65535 ? g : 65535);
-}
-
 
 // ---------------------------------------------------------------------------
-// vectorized variants: V consecutive channels per thread (one 16-byte
-// load per element row) — the decoder's C=16 bf16 layers go from 2-byte
-// to 16-byte access granularity.
+// SplitConvBlock join fused into the statistics pass (T = bf16 or fp16):
+//   x[bs,p,:] = T(T(y_base[b,p,:] + bias[bs,:]) + y_dec[bs,p,:])
+// with bs = b*S + s over rows m = bs*HW + p, plus the per-channel
+// (sum, sumsq) of the ROUNDED x — what bn_stats_vec_kernel would read
+// back. The two explicit roundings reproduce the eager 16-bit add chain
+// bit for bit. (p, bs, b) advance incrementally with the fixed row
+// stride, so the loop has no division.
 // ---------------------------------------------------------------------------
-
-template <typename T, int V>
-struct alignas(sizeof(T) * V) BnVec {
-  T v[V];
-};
-
-inline __host__ __device__ int chan_group_v(int Cv) {
-  int g = 1;
-  while (g < Cv && g < 64) g <<= 1;
-  return g;
-}
 
 template <typename T, int V, bool DET>
 __global__ void __launch_bounds__(kBlock)
-bn_stats_vec_kernel(const T* __restrict__ x, float* __restrict__ sums,
-                    int64_t M, int C, int cgv) {
+bn_join_stats_vec_kernel(const void* __restrict__ y_dec,
+                         const void* __restrict__ y_base,
+                         const void* __restrict__ bias, void* __restrict__ x,
+                         float* __restrict__ sums,  // (2,C)
+                         int64_t M, int HW, int S, int C, int cgv) {
   using Vec = BnVec<T, V>;
-  const int Cv = C / V;
-  const int c0v = blockIdx.y * cgv;
-  const int ncv = min(cgv, Cv - c0v);
-  __shared__ float s_sum[DET ? kBlock * V : 512], s_sq[DET ? kBlock * V : 512];
-  if constexpr (!DET) {
-    for (int i = threadIdx.x; i < cgv * V; i += kBlock) {
-      s_sum[i] = 0.0f;
-      s_sq[i] = 0.0f;
-    }
-    __syncthreads();
-  }
-
-  const int lane_cv = threadIdx.x & (cgv - 1);
-  const int rows_per_blk = kBlock / cgv;
-  const int row0 = blockIdx.x * rows_per_blk + threadIdx.x / cgv;
-  const int rstride = gridDim.x * rows_per_blk;
-  if (lane_cv < ncv) {
-    float acc[V], asq[V];
+  bn_reduce<V, DET, int64_t>(
+      C, cgv, sums, [&](const auto& lm, float (&acc)[V], float (&asq)[V]) {
+        const int Cv = C / V;
+        const Vec* dv = static_cast<const Vec*>(y_dec) + lm.col();
+        const Vec* bv = static_cast<const Vec*>(y_base) + lm.col();
+        const Vec* pv = static_cast<const Vec*>(bias) + lm.col();
+        Vec* xv = static_cast<Vec*>(x) + lm.col();
+        const int64_t row0 = lm.row0();
+        const int rstride = lm.rstride();
+        // row m = bs*HW + p, bs = b*S + s; per-step deltas of (p, s, b)
+        const int dq = rstride / HW, dr = rstride % HW;
+        const int dq_b = dq / S, dq_s = dq % S;
+        int64_t bs = row0 / HW;
+        int p = (int)(row0 - bs * HW);
+        int64_t b = bs / S;
+        int s = (int)(bs - b * S);
+        for (int64_t m = row0; m < M; m += rstride) {
+          const Vec dval = dv[m * Cv];
+          const Vec bval = bv[(b * HW + p) * Cv];
+          const Vec pval = pv[bs * Cv];
+          Vec out;
 #pragma unroll
-    for (int j = 0; j < V; ++j) acc[j] = asq[j] = 0.0f;
-    const Vec* xv = reinterpret_cast<const Vec*>(x);
-    for (int64_t m = row0; m < M; m += rstride) {
-      const Vec val = xv[m * Cv + c0v + lane_cv];
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        const float f = (float)val.v[j];
-        acc[j] += f;
-        asq[j] += f * f;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-      if constexpr (DET) {
-        s_sum[threadIdx.x * V + j] = acc[j];
-        s_sq[threadIdx.x * V + j] = asq[j];
-      } else {
-        atomicAdd(&s_sum[lane_cv * V + j], acc[j]);
-        atomicAdd(&s_sq[lane_cv * V + j], asq[j]);
-      }
-    }
-  }
-  __syncthreads();
-  if constexpr (DET) {
-    det_block_flush(s_sum, s_sq, cgv * V, rows_per_blk, ncv * V, sums, C,
-                    c0v * V);
-    return;
-  }
-  for (int i = threadIdx.x; i < ncv * V; i += kBlock) {
-    atomicAdd(&sums[c0v * V + i], s_sum[i]);
-    atomicAdd(&sums[C + c0v * V + i], s_sq[i]);
-  }
+          for (int j = 0; j < V; ++j) {
+            const T yb = (T)((float)bval.v[j] + (float)pval.v[j]);
+            const T xo = (T)((float)yb + (float)dval.v[j]);
+            out.v[j] = xo;
+            const float f = (float)xo;
+            acc[j] += f;
+            asq[j] += f * f;
+          }
+          xv[m * Cv] = out;
+          p += dr;
+          const int carry = p >= HW ? 1 : 0;
+          p -= carry ? HW : 0;
+          bs += dq + carry;
+          s += dq_s + carry;  // < 2*S: at most one wrap
+          b += dq_b;
+          if (s >= S) {
+            s -= S;
+            ++b;
+          }
+        }
+      });
 }
 
 // ---------------------------------------------------------------------------
-// Lane map shared by every vectorized kernel below (and by
-// bn_stats_vec_kernel above): a thread owns ONE channel vector
-// (lane_cv = tid & (cgv-1), channel chunks of cgv vectors on blockIdx.y)
-// and walks rows m = row0, row0 + rstride, ... with
-// rstride = gridDim.x * (kBlock / cgv). Its per-channel parameters are
-// loaded once into registers before the row loop, so the loop body holds
-// only 16-byte data accesses and arithmetic — no per-element modulo, no
-// parameter loads. cgv is a power of two <= 64; a non-power-of-two Cv
-// (C=24 -> Cv=3) idles the lanes with lane_cv >= ncv.
+// normalize + activation (and the optional residual add), and its backward
 // ---------------------------------------------------------------------------
 
 // Rows each thread keeps in flight in the elementwise kernels (loads
@@ -488,86 +444,6 @@ bn_stats_vec_kernel(const T* __restrict__ x, float* __restrict__ sums,
 // 8 more live registers per row, so it does not unroll.
 constexpr int fwd_unroll(int act) { return act == ACT_ADD_RELU ? 1 : 3; }
 constexpr int dx_unroll(int act) { return act == ACT_ADD_RELU ? 1 : 2; }
-
-template <typename T, int V, int ACT, bool DET>
-__global__ void __launch_bounds__(kBlock)
-bn_act_bwd_reduce_vec_kernel(const T* __restrict__ x,
-                             const T* __restrict__ res,
-                             const T* __restrict__ gy,
-                             const float* __restrict__ mean,
-                             const float* __restrict__ invstd,
-                             const float* __restrict__ gamma,
-                             const float* __restrict__ beta,
-                             float* __restrict__ out,  // (2,C)
-                             int64_t M, int C, int cgv) {
-  using Vec = BnVec<T, V>;
-  const int Cv = C / V;
-  const int c0v = blockIdx.y * cgv;
-  const int ncv = min(cgv, Cv - c0v);
-  __shared__ float s_db[DET ? kBlock * V : 512], s_dg[DET ? kBlock * V : 512];
-  if constexpr (!DET) {
-    for (int i = threadIdx.x; i < cgv * V; i += kBlock) {
-      s_db[i] = 0.0f;
-      s_dg[i] = 0.0f;
-    }
-    __syncthreads();
-  }
-  const int lane_cv = threadIdx.x & (cgv - 1);
-  const int rows_per_blk = kBlock / cgv;
-  const int row0 = blockIdx.x * rows_per_blk + threadIdx.x / cgv;
-  const int rstride = gridDim.x * rows_per_blk;
-  if (lane_cv < ncv) {
-    const int cb = (c0v + lane_cv) * V;
-    float mu[V], is[V], ga[V], be[V], db[V], dg[V];
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-      mu[j] = mean[cb + j];
-      is[j] = invstd[cb + j];
-      ga[j] = gamma[cb + j];
-      be[j] = beta[cb + j];
-      db[j] = dg[j] = 0.0f;
-    }
-    const Vec* xv = reinterpret_cast<const Vec*>(x);
-    const Vec* gv = reinterpret_cast<const Vec*>(gy);
-    const Vec* rv = reinterpret_cast<const Vec*>(res);
-    for (int64_t m = row0; m < M; m += rstride) {
-      const int64_t off = m * Cv + c0v + lane_cv;
-      const Vec xval = xv[off];
-      const Vec gval = gv[off];
-      Vec rval;
-      if constexpr (ACT == ACT_ADD_RELU) rval = rv[off];
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        const float xh = ((float)xval.v[j] - mu[j]) * is[j];
-        float z = xh * ga[j] + be[j];
-        if constexpr (ACT == ACT_ADD_RELU) z += (float)rval.v[j];
-        const float g = (float)gval.v[j] * act_grad_t<ACT>(z);
-        db[j] += g;
-        dg[j] += g * xh;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-      if constexpr (DET) {
-        s_db[threadIdx.x * V + j] = db[j];
-        s_dg[threadIdx.x * V + j] = dg[j];
-      } else {
-        atomicAdd(&s_db[lane_cv * V + j], db[j]);
-        atomicAdd(&s_dg[lane_cv * V + j], dg[j]);
-      }
-    }
-  }
-  __syncthreads();
-  if constexpr (DET) {
-    det_block_flush(s_db, s_dg, cgv * V, rows_per_blk, ncv * V, out, C,
-                    c0v * V);
-    return;
-  }
-  for (int i = threadIdx.x; i < ncv * V; i += kBlock) {
-    atomicAdd(&out[c0v * V + i], s_db[i]);
-    atomicAdd(&out[C + c0v * V + i], s_dg[i]);
-  }
-}
 
 template <typename T, int V, int ACT>
 __device__ __forceinline__ BnVec<T, V> bn_fwd_vec(
@@ -583,24 +459,20 @@ __device__ __forceinline__ BnVec<T, V> bn_fwd_vec(
   return out;
 }
 
+// also the eval-mode kernel: mean/invstd are then the running statistics
 template <typename T, int V, int ACT, int U>
 __global__ void __launch_bounds__(kBlock)
-bn_act_fwd_vec_kernel(const T* __restrict__ x, const T* __restrict__ res,
+bn_act_fwd_vec_kernel(const void* __restrict__ x, const void* __restrict__ res,
                       const float* __restrict__ mean,
                       const float* __restrict__ invstd,
                       const float* __restrict__ gamma,
-                      const float* __restrict__ beta, T* __restrict__ y,
+                      const float* __restrict__ beta, void* __restrict__ y,
                       int64_t M, int C, int cgv) {
   using Vec = BnVec<T, V>;
   const int Cv = C / V;
-  const int c0v = blockIdx.y * cgv;
-  const int ncv = min(cgv, Cv - c0v);
-  const int lane_cv = threadIdx.x & (cgv - 1);
-  if (lane_cv >= ncv) return;
-  const int rows_per_blk = kBlock / cgv;
-  const int64_t row0 = (int64_t)blockIdx.x * rows_per_blk + threadIdx.x / cgv;
-  const int64_t rstride = (int64_t)gridDim.x * rows_per_blk;
-  const int cb = (c0v + lane_cv) * V;
+  const LaneMap<int64_t, int64_t> lm(Cv, cgv);
+  if (!lm.active()) return;
+  const int cb = lm.col() * V;
   float mu[V], is[V], ga[V], be[V];
 #pragma unroll
   for (int j = 0; j < V; ++j) {
@@ -609,12 +481,13 @@ bn_act_fwd_vec_kernel(const T* __restrict__ x, const T* __restrict__ res,
     ga[j] = gamma[cb + j];
     be[j] = beta[cb + j];
   }
-  const Vec* xv = reinterpret_cast<const Vec*>(x) + (c0v + lane_cv);
-  const Vec* rv = reinterpret_cast<const Vec*>(res) + (c0v + lane_cv);
-  Vec* yv = reinterpret_cast<Vec*>(y) + (c0v + lane_cv);
+  const Vec* xv = static_cast<const Vec*>(x) + lm.col();
+  const Vec* rv = static_cast<const Vec*>(res) + lm.col();
+  Vec* yv = static_cast<Vec*>(y) + lm.col();
+  const int64_t rstride = lm.rstride();
   const int64_t step = rstride * Cv;  // vectors between a thread's rows
-  int64_t m = row0;
-  int64_t off = row0 * Cv;
+  int64_t m = lm.row0();
+  int64_t off = lm.row0() * Cv;
   for (; m + (U - 1) * rstride < M; m += U * rstride, off += U * step) {
     Vec xval[U], rval[U];
 #pragma unroll
@@ -656,26 +529,22 @@ __device__ __forceinline__ void bn_dx_vec(
 
 template <typename T, int V, int ACT, int U>
 __global__ void __launch_bounds__(kBlock)
-bn_act_bwd_dx_vec_kernel(const T* __restrict__ x, const T* __restrict__ res,
-                         const T* __restrict__ gy,
+bn_act_bwd_dx_vec_kernel(const void* __restrict__ x,
+                         const void* __restrict__ res,
+                         const void* __restrict__ gy,
                          const float* __restrict__ mean,
                          const float* __restrict__ invstd,
                          const float* __restrict__ gamma,
                          const float* __restrict__ beta,
                          const float* __restrict__ red,  // (2,C)
-                         T* __restrict__ dx, T* __restrict__ dres,
+                         void* __restrict__ dx, void* __restrict__ dres,
                          int64_t M, int C, int cgv) {
   using Vec = BnVec<T, V>;
   const int Cv = C / V;
   const float invM = 1.0f / (float)M;
-  const int c0v = blockIdx.y * cgv;
-  const int ncv = min(cgv, Cv - c0v);
-  const int lane_cv = threadIdx.x & (cgv - 1);
-  if (lane_cv >= ncv) return;
-  const int rows_per_blk = kBlock / cgv;
-  const int64_t row0 = (int64_t)blockIdx.x * rows_per_blk + threadIdx.x / cgv;
-  const int64_t rstride = (int64_t)gridDim.x * rows_per_blk;
-  const int cb = (c0v + lane_cv) * V;
+  const LaneMap<int64_t, int64_t> lm(Cv, cgv);
+  if (!lm.active()) return;
+  const int cb = lm.col() * V;
   float mu[V], is[V], ga[V], be[V], r0[V], r1[V];
 #pragma unroll
   for (int j = 0; j < V; ++j) {
@@ -686,14 +555,15 @@ bn_act_bwd_dx_vec_kernel(const T* __restrict__ x, const T* __restrict__ res,
     r0[j] = red[cb + j];
     r1[j] = red[C + cb + j];
   }
-  const Vec* xv = reinterpret_cast<const Vec*>(x) + (c0v + lane_cv);
-  const Vec* rv = reinterpret_cast<const Vec*>(res) + (c0v + lane_cv);
-  const Vec* gv = reinterpret_cast<const Vec*>(gy) + (c0v + lane_cv);
-  Vec* dxv = reinterpret_cast<Vec*>(dx) + (c0v + lane_cv);
-  Vec* drv = reinterpret_cast<Vec*>(dres) + (c0v + lane_cv);
+  const Vec* xv = static_cast<const Vec*>(x) + lm.col();
+  const Vec* rv = static_cast<const Vec*>(res) + lm.col();
+  const Vec* gv = static_cast<const Vec*>(gy) + lm.col();
+  Vec* dxv = static_cast<Vec*>(dx) + lm.col();
+  Vec* drv = static_cast<Vec*>(dres) + lm.col();
+  const int64_t rstride = lm.rstride();
   const int64_t step = rstride * Cv;
-  int64_t m = row0;
-  int64_t off = row0 * Cv;
+  int64_t m = lm.row0();
+  int64_t off = lm.row0() * Cv;
   for (; m + (U - 1) * rstride < M; m += U * rstride, off += U * step) {
     Vec xval[U], gval[U], rval[U];
 #pragma unroll
@@ -727,104 +597,8 @@ bn_act_bwd_dx_vec_kernel(const T* __restrict__ x, const T* __restrict__ res,
 }
 
 // ---------------------------------------------------------------------------
-// SplitConvBlock join fused into the statistics pass (T = bf16 or fp16):
-//   x[bs,p,:] = T(T(y_base[b,p,:] + bias[bs,:]) + y_dec[bs,p,:])
-// with bs = b*S + s over rows m = bs*HW + p, plus the per-channel
-// (sum, sumsq) of the ROUNDED x — what bn_stats_vec_kernel would read
-// back. The two explicit roundings reproduce the eager 16-bit add chain
-// bit for bit. Same lane map and LDS-then-global-atomic reduction as
-// bn_stats_vec_kernel; (p, bs, b) advance incrementally with the fixed
-// row stride, so the loop has no division.
+// host side
 // ---------------------------------------------------------------------------
-
-template <typename T, int V, bool DET>
-__global__ void __launch_bounds__(kBlock)
-bn_join_stats_vec_kernel(const T* __restrict__ y_dec,
-                         const T* __restrict__ y_base,
-                         const T* __restrict__ bias, T* __restrict__ x,
-                         float* __restrict__ sums,  // (2,C)
-                         int64_t M, int HW, int S, int C, int cgv) {
-  using Vec = BnVec<T, V>;
-  const int Cv = C / V;
-  const int c0v = blockIdx.y * cgv;
-  const int ncv = min(cgv, Cv - c0v);
-  __shared__ float s_sum[DET ? kBlock * V : 512], s_sq[DET ? kBlock * V : 512];
-  if constexpr (!DET) {
-    for (int i = threadIdx.x; i < cgv * V; i += kBlock) {
-      s_sum[i] = 0.0f;
-      s_sq[i] = 0.0f;
-    }
-    __syncthreads();
-  }
-
-  const int lane_cv = threadIdx.x & (cgv - 1);
-  const int rows_per_blk = kBlock / cgv;
-  const int64_t row0 = (int64_t)blockIdx.x * rows_per_blk + threadIdx.x / cgv;
-  const int rstride = gridDim.x * rows_per_blk;  // <= kMaxGridReduce * 256
-  if (lane_cv < ncv) {
-    float acc[V], asq[V];
-#pragma unroll
-    for (int j = 0; j < V; ++j) acc[j] = asq[j] = 0.0f;
-    const int col = c0v + lane_cv;
-    const Vec* dv = reinterpret_cast<const Vec*>(y_dec) + col;
-    const Vec* bv = reinterpret_cast<const Vec*>(y_base) + col;
-    const Vec* pv = reinterpret_cast<const Vec*>(bias) + col;
-    Vec* xv = reinterpret_cast<Vec*>(x) + col;
-    // row m = bs*HW + p, bs = b*S + s; per-step deltas of (p, s, b)
-    const int dq = rstride / HW, dr = rstride % HW;
-    const int dq_b = dq / S, dq_s = dq % S;
-    int64_t bs = row0 / HW;
-    int p = (int)(row0 - bs * HW);
-    int64_t b = bs / S;
-    int s = (int)(bs - b * S);
-    for (int64_t m = row0; m < M; m += rstride) {
-      const Vec dval = dv[m * Cv];
-      const Vec bval = bv[(b * HW + p) * Cv];
-      const Vec pval = pv[bs * Cv];
-      Vec out;
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        const T yb = (T)((float)bval.v[j] + (float)pval.v[j]);
-        const T xo = (T)((float)yb + (float)dval.v[j]);
-        out.v[j] = xo;
-        const float f = (float)xo;
-        acc[j] += f;
-        asq[j] += f * f;
-      }
-      xv[m * Cv] = out;
-      p += dr;
-      const int carry = p >= HW ? 1 : 0;
-      p -= carry ? HW : 0;
-      bs += dq + carry;
-      s += dq_s + carry;  // < 2*S: at most one wrap
-      b += dq_b;
-      if (s >= S) {
-        s -= S;
-        ++b;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-      if constexpr (DET) {
-        s_sum[threadIdx.x * V + j] = acc[j];
-        s_sq[threadIdx.x * V + j] = asq[j];
-      } else {
-        atomicAdd(&s_sum[lane_cv * V + j], acc[j]);
-        atomicAdd(&s_sq[lane_cv * V + j], asq[j]);
-      }
-    }
-  }
-  __syncthreads();
-  if constexpr (DET) {
-    det_block_flush(s_sum, s_sq, cgv * V, rows_per_blk, ncv * V, sums, C,
-                    c0v * V);
-    return;
-  }
-  for (int i = threadIdx.x; i < ncv * V; i += kBlock) {
-    atomicAdd(&sums[c0v * V + i], s_sum[i]);
-    atomicAdd(&sums[C + c0v * V + i], s_sq[i]);
-  }
-}
 
 // grid.x caps. The reductions keep 2048 blocks: the cap fixes which rows
 // a thread sums, so keeping it keeps the summation grouping, and the
@@ -850,24 +624,20 @@ inline dim3 grid_rows_v(int64_t M, int Cv, int cgv, int cap, int max_blocks) {
       (Cv + cgv - 1) / cgv);
 }
 
-inline dim3 grid_reduce_v(int64_t M, int Cv, int cgv, int max_blocks) {
-  return grid_rows_v(M, Cv, cgv, kMaxGridReduce, max_blocks);
-}
-
-inline dim3 grid_stream_v(int64_t M, int Cv, int cgv, int max_blocks) {
-  return grid_rows_v(M, Cv, cgv, kMaxGridStream, max_blocks);
-}
-
-inline dim3 grid_reduce(int64_t M, int C, int cg, int max_blocks) {
-  // enough slabs to fill 256 CUs x a few blocks, bounded
-  return grid_rows_v(M, C, cg, kMaxGridReduce, max_blocks);
-}
-
-inline dim3 grid_elems_capped(int64_t total, int max_blocks) {
-  int g = grid_elems(total);
-  if (max_blocks > 0 && g > max_blocks) g = max_blocks;
-  return dim3(g);
-}
+// Run the statements with V, Cv and cgv bound for (T, C): V is 16 bytes of
+// T when C is a multiple of that, else 1.
+#define BN_VEC_CASE(VEC, C, ...)    \
+  {                                 \
+    constexpr int V = VEC;          \
+    const int Cv = (C) / V;         \
+    const int cgv = chan_group(Cv); \
+    __VA_ARGS__;                    \
+  }
+#define BN_VEC_SWITCH(T, C, ...)                         \
+  if ((C) % (16 / (int)sizeof(T)) == 0)                  \
+    BN_VEC_CASE(16 / (int)sizeof(T), C, __VA_ARGS__)     \
+  else                                                   \
+    BN_VEC_CASE(1, C, __VA_ARGS__)
 
 // the host switches on `act` once; the kernels take it as a template
 // parameter
@@ -884,32 +654,20 @@ inline dim3 grid_elems_capped(int64_t total, int max_blocks) {
 // workspace has that many (2, C) partials.
 template <typename T>
 int reduce_grid_x(int64_t M, int C, int max_blocks) {
-  constexpr int V = 16 / (int)sizeof(T);
-  if (C % V == 0) {
-    const int Cv = C / V;
-    return (int)grid_reduce_v(M, Cv, chan_group_v(Cv), max_blocks).x;
-  }
-  return (int)grid_reduce(M, C, chan_group(C), max_blocks).x;
+  BN_VEC_SWITCH(
+      T, C, return (int)grid_rows_v(M, Cv, cgv, kMaxGridReduce, max_blocks).x)
 }
 
 // DET: `sums` is the [grid.x][2][C] workspace (no zero fill needed)
 template <typename T, bool DET>
 void launch_bn_stats(const void* x, float* sums, int64_t M, int C,
                      int max_blocks, hipStream_t s) {
-  constexpr int V = 16 / (int)sizeof(T);
-  const T* xp = reinterpret_cast<const T*>(x);
-  if (C % V == 0) {
-    const int Cv = C / V;
-    const int cgv = chan_group_v(Cv);
-    hipLaunchKernelGGL((bn_stats_vec_kernel<T, V, DET>),
-                       grid_reduce_v(M, Cv, cgv, max_blocks), dim3(kBlock), 0,
-                       s, xp, sums, M, C, cgv);
-    return;
-  }
-  const int cg = chan_group(C);
-  hipLaunchKernelGGL((bn_stats_kernel<T, DET>),
-                     grid_reduce(M, C, cg, max_blocks), dim3(kBlock), 0, s, xp,
-                     sums, M, C, cg);
+  BN_VEC_SWITCH(
+      T, C,
+      hipLaunchKernelGGL(
+          (bn_stats_vec_kernel<T, V, DET>),
+          grid_rows_v(M, Cv, cgv, kMaxGridReduce, max_blocks), dim3(kBlock), 0,
+          s, x, sums, M, C, cgv))
 }
 
 template <typename T>
@@ -917,25 +675,13 @@ void launch_bn_act_fwd(const void* x, const void* res, const float* mean,
                        const float* invstd, const float* gamma,
                        const float* beta, void* y, int64_t M, int C, int act,
                        int max_blocks, hipStream_t s) {
-  constexpr int V = 16 / (int)sizeof(T);
-  const T* xp = reinterpret_cast<const T*>(x);
-  const T* rp = reinterpret_cast<const T*>(res);
-  T* yp = reinterpret_cast<T*>(y);
-  if (C % V == 0) {
-    const int Cv = C / V;
-    const int cgv = chan_group_v(Cv);
-    const dim3 grid = grid_stream_v(M, Cv, cgv, max_blocks);
-#define BN_LAUNCH(A)                                                         \
-  hipLaunchKernelGGL((bn_act_fwd_vec_kernel<T, V, A, fwd_unroll(A)>), grid,     \
-                     dim3(kBlock), 0, s, xp, rp, mean, invstd, gamma, beta,  \
-                     yp, M, C, cgv)
-    BN_ACT_SWITCH(act, BN_LAUNCH)
+#define BN_LAUNCH(A)                                                          \
+  hipLaunchKernelGGL((bn_act_fwd_vec_kernel<T, V, A, fwd_unroll(A)>),         \
+                     grid_rows_v(M, Cv, cgv, kMaxGridStream, max_blocks),     \
+                     dim3(kBlock), 0, s, x, res, mean, invstd, gamma, beta, y, \
+                     M, C, cgv)
+  BN_VEC_SWITCH(T, C, BN_ACT_SWITCH(act, BN_LAUNCH))
 #undef BN_LAUNCH
-    return;
-  }
-  hipLaunchKernelGGL(bn_act_fwd_kernel<T>,
-                     grid_elems_capped(M * C, max_blocks), dim3(kBlock), 0, s,
-                     xp, rp, mean, invstd, gamma, beta, yp, M, C, act);
 }
 
 // DET: `out` is the [grid.x][2][C] workspace
@@ -945,26 +691,13 @@ void launch_bn_act_bwd_reduce(const void* x, const void* res, const void* gy,
                               const float* gamma, const float* beta,
                               float* out, int64_t M, int C, int act,
                               int max_blocks, hipStream_t s) {
-  constexpr int V = 16 / (int)sizeof(T);
-  const T* xp = reinterpret_cast<const T*>(x);
-  const T* rp = reinterpret_cast<const T*>(res);
-  const T* gp = reinterpret_cast<const T*>(gy);
-  if (C % V == 0) {
-    const int Cv = C / V;
-    const int cgv = chan_group_v(Cv);
-    const dim3 grid = grid_reduce_v(M, Cv, cgv, max_blocks);
-#define BN_LAUNCH(A)                                                        \
-  hipLaunchKernelGGL((bn_act_bwd_reduce_vec_kernel<T, V, A, DET>), grid,    \
-                     dim3(kBlock), 0, s, xp, rp, gp, mean, invstd, gamma,   \
+#define BN_LAUNCH(A)                                                       \
+  hipLaunchKernelGGL((bn_act_bwd_reduce_vec_kernel<T, V, A, DET>),         \
+                     grid_rows_v(M, Cv, cgv, kMaxGridReduce, max_blocks),  \
+                     dim3(kBlock), 0, s, x, res, gy, mean, invstd, gamma,  \
                      beta, out, M, C, cgv)
-    BN_ACT_SWITCH(act, BN_LAUNCH)
+  BN_VEC_SWITCH(T, C, BN_ACT_SWITCH(act, BN_LAUNCH))
 #undef BN_LAUNCH
-    return;
-  }
-  const int cg = chan_group(C);
-  hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<T, DET>),
-                     grid_reduce(M, C, cg, max_blocks), dim3(kBlock), 0, s, xp,
-                     rp, gp, mean, invstd, gamma, beta, out, M, C, act, cg);
 }
 
 template <typename T>
@@ -973,28 +706,13 @@ void launch_bn_act_bwd_dx(const void* x, const void* res, const void* gy,
                           const float* gamma, const float* beta,
                           const float* red, void* dx, void* dres, int64_t M,
                           int C, int act, int max_blocks, hipStream_t s) {
-  constexpr int V = 16 / (int)sizeof(T);
-  const T* xp = reinterpret_cast<const T*>(x);
-  const T* rp = reinterpret_cast<const T*>(res);
-  const T* gp = reinterpret_cast<const T*>(gy);
-  T* dxp = reinterpret_cast<T*>(dx);
-  T* drp = reinterpret_cast<T*>(dres);
-  if (C % V == 0) {
-    const int Cv = C / V;
-    const int cgv = chan_group_v(Cv);
-    const dim3 grid = grid_stream_v(M, Cv, cgv, max_blocks);
-#define BN_LAUNCH(A)                                                         \
-  hipLaunchKernelGGL((bn_act_bwd_dx_vec_kernel<T, V, A, dx_unroll(A)>), grid,   \
-                     dim3(kBlock), 0, s, xp, rp, gp, mean, invstd, gamma,    \
-                     beta, red, dxp, drp, M, C, cgv)
-    BN_ACT_SWITCH(act, BN_LAUNCH)
+#define BN_LAUNCH(A)                                                        \
+  hipLaunchKernelGGL((bn_act_bwd_dx_vec_kernel<T, V, A, dx_unroll(A)>),     \
+                     grid_rows_v(M, Cv, cgv, kMaxGridStream, max_blocks),   \
+                     dim3(kBlock), 0, s, x, res, gy, mean, invstd, gamma,   \
+                     beta, red, dx, dres, M, C, cgv)
+  BN_VEC_SWITCH(T, C, BN_ACT_SWITCH(act, BN_LAUNCH))
 #undef BN_LAUNCH
-    return;
-  }
-  hipLaunchKernelGGL(bn_act_bwd_dx_kernel<T>,
-                     grid_elems_capped(M * C, max_blocks), dim3(kBlock), 0, s,
-                     xp, rp, gp, mean, invstd, gamma, beta, red, dxp, drp, M,
-                     C, act);
 }
 
 // x = T(T(y_base + bias) + y_dec) and its (sum, sumsq); C % 8 == 0
@@ -1003,15 +721,12 @@ void launch_bn_join_stats(const void* y_dec, const void* y_base,
                           const void* bias, void* x, float* sums, int64_t M,
                           int HW, int S, int C, int max_blocks,
                           hipStream_t s) {
-  constexpr int V = 8;
-  const int Cv = C / V;
-  const int cgv = chan_group_v(Cv);
-  hipLaunchKernelGGL((bn_join_stats_vec_kernel<T, V, DET>),
-                     grid_reduce_v(M, Cv, cgv, max_blocks), dim3(kBlock), 0, s,
-                     reinterpret_cast<const T*>(y_dec),
-                     reinterpret_cast<const T*>(y_base),
-                     reinterpret_cast<const T*>(bias), reinterpret_cast<T*>(x),
-                     sums, M, HW, S, C, cgv);
+  BN_VEC_CASE(
+      8, C,
+      hipLaunchKernelGGL(
+          (bn_join_stats_vec_kernel<T, V, DET>),
+          grid_rows_v(M, Cv, cgv, kMaxGridReduce, max_blocks), dim3(kBlock), 0,
+          s, y_dec, y_base, bias, x, sums, M, HW, S, C, cgv))
 }
 
 }  // namespace

@@ -1,6 +1,7 @@
-"""Fused BN+activation stream kernels: lane-map cases of the vectorized
-path (bf16 V=8, fp32 V=4), forced small grids, eval mode, the fused
-SplitConvBlock join and its decoder-level equivalence with the eager join.
+"""Fused BN+activation stream kernels: lane-map cases (bf16 V=8, fp32
+V=4, and V=1 where C is no multiple of that), forced small grids, eval
+mode, the fused SplitConvBlock join and its decoder-level equivalence
+with the eager join.
 
 Oracle and tolerances follow tests/test_gpu_ops.py
 (test_fused_bn_act_matches_torch / test_fused_bn_add_relu_matches_torch):
@@ -27,9 +28,18 @@ SHAPES_BOTH = [
     (1, 16, 1, 1),     # M=1
 ]
 SHAPES_F32_ONLY = [(3, 4, 5, 7), (2, 12, 5, 7)]  # fp32 Cv=1 and Cv=3
+# C no multiple of 16 bytes: one channel per thread (V=1)
+SHAPES_V1_BF16 = [
+    (2, 12, 5, 7),     # group of 16 with four idle lanes
+    (1, 70, 3, 3),     # two channel chunks, the second partial
+    (1, 12, 1, 1),     # M=1
+]
+SHAPES_V1_F32 = [(2, 6, 5, 7)]
 
 PARITY_CASES = [(torch.bfloat16, s) for s in SHAPES_BOTH] + \
-    [(torch.float32, s) for s in SHAPES_BOTH + SHAPES_F32_ONLY]
+    [(torch.float32, s) for s in SHAPES_BOTH + SHAPES_F32_ONLY] + \
+    [(torch.bfloat16, s) for s in SHAPES_V1_BF16] + \
+    [(torch.float32, s) for s in SHAPES_V1_F32]
 
 
 def _tol(dtype):
@@ -101,11 +111,13 @@ def test_module_parity(act, dtype, shape):
 
 # (3,16,9,15) is added to the two shapes the lane-map table names: with
 # one block a bf16 thread then owns four rows, so the unrolled body of
-# the fwd kernel (three rows) runs as well as its tail.
+# the fwd kernel (three rows) runs as well as its tail. (2,12,9,11) is
+# V=1 in both types: with one block a thread owns 12 or 13 rows, so the
+# unrolled bodies of fwd (three rows) and dx (two) and both tails run.
 @pytest.mark.parametrize("act", ["elu", "add_relu"])
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 @pytest.mark.parametrize("shape", [(2, 16, 9, 11), (2, 24, 5, 7),
-                                   (3, 16, 9, 15)])
+                                   (3, 16, 9, 15), (2, 12, 9, 11)])
 def test_forced_small_grid(shape, dtype, act):
     from mine_amd.ops.backend import get_extension
     from mine_amd.ops.bn import _ACT

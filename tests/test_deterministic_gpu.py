@@ -27,14 +27,15 @@ SHAPES_BOTH = [
     (1, 16, 1, 1),
 ]
 SHAPES_F32_ONLY = [(3, 4, 5, 7), (2, 12, 5, 7)]
-GENERIC_BF16 = (2, 12, 5, 7)     # C % 8 != 0: the generic kernel
+GENERIC_BF16 = (2, 12, 5, 7)     # C % 8 != 0: one channel per thread (V=1)
 BIG_BF16 = (4, 16, 96, 128)      # 384 blocks without forcing
 
 SUM_CASES = [(BF16, s) for s in SHAPES_BOTH] + \
     [(F32, s) for s in SHAPES_BOTH + SHAPES_F32_ONLY] + \
-    [(BF16, GENERIC_BF16), (BF16, BIG_BF16)]
+    [(BF16, GENERIC_BF16), (BF16, BIG_BF16)] + \
+    [(F32, (2, 6, 5, 7)), (BF16, (1, 70, 3, 3))]    # V=1 as well
 PARITY_CASES = [(BF16, s) for s in SHAPES_BOTH] + \
-    [(F32, s) for s in SHAPES_BOTH]
+    [(F32, s) for s in SHAPES_BOTH] + [(BF16, GENERIC_BF16)]
 
 
 def _id(case):

@@ -61,9 +61,14 @@ def _module(C, act, d):
     return m
 
 
-@pytest.mark.parametrize("act", ACTS)
-@pytest.mark.parametrize("shape", SHAPES,
-                         ids=["x".join(map(str, s)) for s in SHAPES])
+# C=12 is no multiple of 8: one channel per thread (V=1)
+PARITY_TRAIN = [(a, s) for s in SHAPES for a in ACTS] + \
+    [(a, (2, 12, 5, 7)) for a in ("elu", "add_relu")]
+
+
+@pytest.mark.parametrize(
+    "act,shape", PARITY_TRAIN,
+    ids=[f"{'x'.join(map(str, s))}-{a}" for a, s in PARITY_TRAIN])
 def test_module_parity_train(act, shape):
     B, C, H, W = shape
     d = _inputs(shape)
