@@ -38,6 +38,7 @@ from mine_amd.ops import (
     psnr,
     render_src_view,
     render_tgt_view,
+    render_tgt_views,
     sample_disparity_from_bins,
     sample_disparity_linspace,
     sample_pdf,
@@ -266,15 +267,34 @@ class SynthesisTask:
         """Stage a batch on the device (ref synthesis_task.py:184-209).
 
         static=True copies into persistent device buffers (same shapes
-        every step) — the staging the hipGraph-captured step reads."""
+        every step) — the staging the hipGraph-captured step reads.
+
+        The target side arrives as B x L views per sample
+        (data.num_tgt_views). The reference asserts L == 1 for memory (ref
+        synthesis_task.py:200-201); here the L cameras share one MPI
+        (ops.render_tgt_views), so L > 1 is staged view-major and
+        flattened to (L*B, ...): index l*B + b is view l of sample b, and
+        every [l*B:(l+1)*B] slice is an ordinary batch."""
         src_items, tgt_items = items
         dev = self.device
 
         def tod(x):
             return x.to(dev, non_blocking=True)
 
-        L = tgt_items["img"].shape[1]
-        assert L == 1, "one target supervision view (ref synthesis_task.py:200-201)"
+        B, L = tgt_items["img"].shape[:2]
+        assert L >= 1, "at least one target supervision view"
+        if static and L != 1:
+            raise NotImplementedError(
+                "static staging (the captured train step) takes one target "
+                f"view per sample, got data.num_tgt_views = {L}; run the "
+                "eager train_step for several views")
+        self.num_tgt_views = L
+
+        def tgt(x):
+            x = tod(x).float()
+            if L == 1:
+                return x.squeeze(1)
+            return x.transpose(0, 1).reshape((L * B,) + tuple(x.shape[2:]))
 
         if static and getattr(self, "_static_staged", False):
             self.src_imgs.copy_(src_items["img"], non_blocking=True)
@@ -297,11 +317,11 @@ class SynthesisTask:
         self.K_src_inv = tod(src_items["K_inv"]).float()
         self.pt3d_src = tod(src_items["xyzs"]).float()  # Bx3xN_pt
 
-        self.tgt_imgs = tod(tgt_items["img"]).float().squeeze(1)
-        self.G_src_tgt = tod(tgt_items["G_src_tgt"]).float().squeeze(1)
-        self.K_tgt = tod(tgt_items["K"]).float().squeeze(1)
-        self.K_tgt_inv = tod(tgt_items["K_inv"]).float().squeeze(1)
-        self.pt3d_tgt = tod(tgt_items["xyzs"]).float().squeeze(1)
+        self.tgt_imgs = tgt(tgt_items["img"])
+        self.G_src_tgt = tgt(tgt_items["G_src_tgt"])
+        self.K_tgt = tgt(tgt_items["K"])
+        self.K_tgt_inv = tgt(tgt_items["K_inv"])
+        self.pt3d_tgt = tgt(tgt_items["xyzs"])
 
         # closed-form rigid inverse (the reference retried torch.inverse
         # around cuda.synchronize here; ref synthesis_task.py:208-209)
@@ -371,17 +391,33 @@ class SynthesisTask:
                           G_tgt_src: torch.Tensor, K_src_inv: torch.Tensor,
                           K_tgt: torch.Tensor, scale_factor=None
                           ) -> Dict[str, torch.Tensor]:
-        """Scale-factored novel-view render (ref synthesis_task.py:435-474)."""
+        """Scale-factored novel-view render (ref synthesis_task.py:435-474).
+
+        G_tgt_src and K_tgt of (V*B, ...) with V > 1 hold V views per
+        sample, view-major: the V cameras read the one MPI through
+        render_tgt_views, the outputs come back as (V*B, ...), and the
+        per-sample scale_factor (B) is repeated over the views."""
+        B = mpi_packed.shape[0]
+        V = G_tgt_src.shape[0] // B
         if scale_factor is not None:
             with torch.no_grad():
                 G_tgt_src = G_tgt_src.clone()
                 sf = scale_factor if torch.is_tensor(scale_factor) else \
                     torch.as_tensor(scale_factor, dtype=torch.float32,
                                     device=G_tgt_src.device)
+                if V > 1 and sf.numel() == B:
+                    sf = sf.repeat(V)
                 G_tgt_src[:, 0:3, 3] = G_tgt_src[:, 0:3, 3] / sf.view(-1, 1)
-        tgt_rgb, tgt_depth, tgt_mask = render_tgt_view(
-            mpi_packed, disparity, G_tgt_src, K_src_inv, K_tgt,
-            bg_depth_inf=self.bg_depth_inf, use_alpha=self.use_alpha)
+        if V > 1:
+            outs = render_tgt_views(
+                mpi_packed, disparity, G_tgt_src.reshape(V, B, 4, 4),
+                K_src_inv, K_tgt.reshape(V, B, 3, 3),
+                bg_depth_inf=self.bg_depth_inf, use_alpha=self.use_alpha)
+            tgt_rgb, tgt_depth, tgt_mask = (o.flatten(0, 1) for o in outs)
+        else:
+            tgt_rgb, tgt_depth, tgt_mask = render_tgt_view(
+                mpi_packed, disparity, G_tgt_src, K_src_inv, K_tgt,
+                bg_depth_inf=self.bg_depth_inf, use_alpha=self.use_alpha)
         return {"tgt_imgs_syn": tgt_rgb,
                 "tgt_disparity_syn": torch.reciprocal(tgt_depth),
                 "tgt_mask_syn": tgt_mask}
@@ -471,7 +507,11 @@ class SynthesisTask:
         tgt_pt3d_pxpy = torch.matmul(K_tgt_scaled, self.pt3d_tgt)
         tgt_pt3d_pxpy = tgt_pt3d_pxpy[:, 0:2] / tgt_pt3d_pxpy[:, 2:]
         tgt_pt3d_disp_syn = gather_pixel_by_pxpy(tgt_disparity_syn, tgt_pt3d_pxpy)
-        tgt_pt3d_disp_syn_scaled = tgt_pt3d_disp_syn / scale_factor.view(B, 1, 1)
+        # one scale factor per sample (from the source view), repeated over
+        # the target views of the (L*B) batch
+        L = tgt_scaled.shape[0] // B
+        sf_tgt = scale_factor if L == 1 else scale_factor.repeat(L)
+        tgt_pt3d_disp_syn_scaled = tgt_pt3d_disp_syn / sf_tgt.view(L * B, 1, 1)
         loss_disp_pt3dtgt = disp_lambda * torch.mean(torch.abs(
             torch.log(tgt_pt3d_disp_syn_scaled) - torch.log(tgt_pt3d_disp)))
 

@@ -9,6 +9,8 @@ Public API (device-dispatched):
                         into a novel view (ref operations/
                         homography_sampler.py:58-141 +
                         mpi_rendering.py:181-241, fused)
+    render_tgt_views  — the same for V cameras that read ONE MPI: one
+                        forward launch, one MPI-sized gradient buffer
     sample_disparity* — stratified disparity sampling
     sample_pdf        — inverse-CDF hierarchical sampling
     gather_pixel_by_pxpy, ssim, edge-aware losses, psnr
@@ -34,7 +36,11 @@ from mine_amd.ops.backend import (  # noqa: F401
     is_deterministic,
     set_deterministic,
 )
-from mine_amd.ops.renderer import render_src_view, render_tgt_view  # noqa: F401
+from mine_amd.ops.renderer import (  # noqa: F401
+    render_src_view,
+    render_tgt_view,
+    render_tgt_views,
+)
 from mine_amd.ops.sparse import gather_pixel_by_pxpy  # noqa: F401
 from mine_amd.ops.ssim import ssim  # noqa: F401
 from mine_amd.ops.losses import (  # noqa: F401

@@ -285,6 +285,88 @@ at::Tensor tgt_composite_bwd(at::Tensor mpi, at::Tensor hinv, at::Tensor hfwd,
   return grad_mpi;
 }
 
+// View-batched novel-view render: V cameras read ONE mpi (B,S,H,W,4).
+// Geometry and outputs are view-major, row v*B + b: hinv (V,B,S,3,3),
+// m (V,B,3,3), tvec (V,B,3); depths (B,S) belongs to the MPI.
+
+// the checks both view-batched bindings share; returns the MPI geometry
+MpiGeom check_views(const char* who, const at::Tensor& mpi,
+                    const at::Tensor& hinv, const at::Tensor& m,
+                    const at::Tensor& tvec, const at::Tensor& depths,
+                    int64_t V) {
+  const MpiGeom g = check_mpi(who, "mpi", mpi, kMaxPlanes);
+  TORCH_CHECK(g.H * g.W * 4 < (int64_t(1) << 31), who,
+              ": one plane must stay below 2^31 floats (32-bit tap offsets)");
+  TORCH_CHECK(V >= 1, who, ": views must be at least 1, got ", V);
+  TORCH_CHECK(V * g.B <= 65535, who, ": views * B too large for the grid");
+  check_arg(who, "hinv", hinv, mpi, kF32, V * g.B * g.S * 9);
+  check_arg(who, "m", m, mpi, kF32, V * g.B * 9);
+  check_arg(who, "tvec", tvec, mpi, kF32, V * g.B * 3);
+  check_arg(who, "depths", depths, mpi, kF32, g.B * g.S);
+  return g;
+}
+
+std::vector<at::Tensor> tgt_views_fwd(at::Tensor mpi, at::Tensor hinv,
+                                      at::Tensor m, at::Tensor tvec,
+                                      at::Tensor depths, int64_t views,
+                                      bool bg_inf, bool alpha) {
+  const char* who = "tgt_views_fwd";
+  const int64_t V = views;
+  const auto [B, S, H, W] = check_views(who, mpi, hinv, m, tvec, depths, V);
+  auto rgb = at::empty({V, B, 3, H, W}, mpi.options());
+  auto depth = at::empty({V, B, 1, H, W}, mpi.options());
+  auto mask = at::empty({V, B, 1, H, W}, mpi.options());
+  mine_tgt_views_fwd(mpi.data_ptr<float>(), hinv.data_ptr<float>(),
+                     m.data_ptr<float>(), tvec.data_ptr<float>(),
+                     depths.data_ptr<float>(), rgb.data_ptr<float>(),
+                     depth.data_ptr<float>(), mask.data_ptr<float>(), (int)V,
+                     (int)B, (int)S, (int)H, (int)W, bg_inf ? 1 : 0,
+                     alpha ? 1 : 0, stream());
+  launched(who);
+  return {rgb, depth, mask};
+}
+
+// Modes as tgt_composite_bwd. ONE grad_mpi and ONE payload, both the
+// size of the MPI, serve all V views: the launcher runs the views in
+// stream order. g_rgb (V,B,3,H,W) and g_depth (V,B,1,H,W) may be empty.
+// workspace as there: contents on entry do not matter.
+at::Tensor tgt_views_bwd(at::Tensor mpi, at::Tensor hinv, at::Tensor hfwd,
+                         at::Tensor m, at::Tensor tvec, at::Tensor depths,
+                         int64_t views, bool bg_inf, bool alpha,
+                         at::Tensor g_rgb, at::Tensor g_depth, int64_t mode,
+                         c10::optional<at::Tensor> workspace) {
+  const char* who = "tgt_views_bwd";
+  const int64_t V = views;
+  const auto [B, S, H, W] = check_views(who, mpi, hinv, m, tvec, depths, V);
+  TORCH_CHECK(mode >= 0 && mode <= 2, who, ": unknown mode");
+  const float* g_rgb_p =
+      opt_arg<const float>(who, "g_rgb", g_rgb, mpi, kF32, V * B * 3 * H * W);
+  const float* g_depth_p =
+      opt_arg<const float>(who, "g_depth", g_depth, mpi, kF32, V * B * H * W);
+  at::Tensor payload;
+  if (mode >= 1) {
+    check_arg(who, "hfwd", hfwd, mpi, kF32, V * B * S * 9);
+    if (workspace.has_value()) {
+      payload = *workspace;
+      check_arg(who, "workspace", payload, mpi, kF32, mpi.numel());
+    } else {
+      payload = at::empty_like(mpi);
+    }
+  }
+  // mode 2: view 0's collect pass stores every entry, later views add
+  auto grad_mpi = mode == 2 ? at::empty_like(mpi) : at::zeros_like(mpi);
+  mine_tgt_views_bwd(mpi.data_ptr<float>(), hinv.data_ptr<float>(),
+                     mode >= 1 ? hfwd.data_ptr<float>() : nullptr,
+                     m.data_ptr<float>(), tvec.data_ptr<float>(),
+                     depths.data_ptr<float>(), g_rgb_p, g_depth_p,
+                     grad_mpi.data_ptr<float>(),
+                     mode >= 1 ? payload.data_ptr<float>() : nullptr, (int)V,
+                     (int)B, (int)S, (int)H, (int)W, bg_inf ? 1 : 0, (int)mode,
+                     alpha ? 1 : 0, stream());
+  launched(who);
+  return grad_mpi;
+}
+
 // collect pass of the order-fixed warp backward alone, on a caller's
 // payload (B,S,H,W,4): grad_mpi[b,s,q] = sum over the target pixels whose
 // bilinear taps hit source texel q, in raster order
@@ -1050,6 +1132,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "collect pass of the order-fixed warp backward on a given payload",
           pybind11::arg("payload"), pybind11::arg("hinv"),
           pybind11::arg("hfwd"));
+  // The top-level names are the single-view bindings, one row each in
+  // the table of tests/test_binding_checks.py. The view-batched renderer
+  // (a view count, view-major geometry) sits in a submodule; its refusal
+  // table is in tests/test_render_views_gpu.py.
+  auto views = mod.def_submodule(
+      "_views", "novel-view render of V cameras from one MPI");
+  views.def("tgt_views_fwd", &tgt_views_fwd, pybind11::arg("mpi"),
+            pybind11::arg("hinv"), pybind11::arg("m"), pybind11::arg("tvec"),
+            pybind11::arg("depths"), pybind11::arg("views"),
+            pybind11::arg("bg_inf"), pybind11::arg("alpha"));
+  views.def("tgt_views_bwd", &tgt_views_bwd, pybind11::arg("mpi"),
+            pybind11::arg("hinv"), pybind11::arg("hfwd"), pybind11::arg("m"),
+            pybind11::arg("tvec"), pybind11::arg("depths"),
+            pybind11::arg("views"), pybind11::arg("bg_inf"),
+            pybind11::arg("alpha"), pybind11::arg("g_rgb"),
+            pybind11::arg("g_depth"), pybind11::arg("mode"),
+            pybind11::arg("workspace") = pybind11::none());
   mod.def("ssim_fwd", &ssim_fwd, pybind11::arg("img1"), pybind11::arg("img2"),
           pybind11::arg("det") = false);
   mod.def("ssim_bwd", &ssim_bwd);

@@ -98,6 +98,28 @@ void mine_tgt_composite_bwd(const float* mpi, const float* hinv,
                             float* grad_mpi, float* payload, int B, int S,
                             int H, int W, int bg_inf, int mode, int alpha,
                             hipStream_t stream);
+// V cameras read one MPI. Geometry and outputs are view-major with row
+// r = v*B + b: hinv (V*B,S,3,3), m_rki (V*B,3,3), tvec (V*B,3) -> rgb_out
+// (V*B,3,H,W), depth_out and mask_out (V*B,1,H,W). Row r reads mpi
+// (B,S,H,W,4) and depths (B,S) at r % B. One launch of the kernel of
+// mine_tgt_composite_fwd; V*B <= 65535, other limits as there.
+void mine_tgt_views_fwd(const float* mpi, const float* hinv,
+                        const float* m_rki, const float* tvec,
+                        const float* depths, float* rgb_out, float* depth_out,
+                        float* mask_out, int V, int B, int S, int H, int W,
+                        int bg_inf, int alpha, hipStream_t stream);
+// Backward of the above into ONE grad_mpi (B,S,H,W,4) through ONE payload
+// (B,S,H,W,4): the kernels of mine_tgt_composite_bwd run view after view
+// in stream order at row offset v*B. hfwd (V*B,S,3,3), g_rgb (V*B,3,H,W)
+// and g_depth (V*B,1,H,W) may be null as there; fills as there (modes 0
+// and 1 zero-filled once, mode 2 none: view 0 stores, later views add in
+// ascending order with the accumulate form of the collect pass).
+void mine_tgt_views_bwd(const float* mpi, const float* hinv, const float* hfwd,
+                        const float* m_rki, const float* tvec,
+                        const float* depths, const float* g_rgb,
+                        const float* g_depth, float* grad_mpi, float* payload,
+                        int V, int B, int S, int H, int W, int bg_inf,
+                        int mode, int alpha, hipStream_t stream);
 // collect pass alone: payload (B,S,H,W,4), hinv and hfwd (B,S,3,3) ->
 // grad_mpi (B,S,H,W,4), no fill needed. B, S <= 65535.
 void mine_tgt_collect(const float* payload, const float* hinv,

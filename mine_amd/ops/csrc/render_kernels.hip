@@ -445,20 +445,26 @@ DEV float plane_delta(float3 a, float3 b) {
 
 template <bool BG_INF, bool ALPHA = false>
 __global__ void __launch_bounds__(kBlock)
-tgt_composite_fwd_kernel(const float* __restrict__ mpi,
-                         const float* __restrict__ hinv,    // (B,S,3,3)
-                         const float* __restrict__ m_rki,   // (B,3,3)
-                         const float* __restrict__ tvec,    // (B,3)
-                         const float* __restrict__ depths,  // (B,S)
-                         float* __restrict__ rgb_out,
-                         float* __restrict__ depth_out,
-                         float* __restrict__ mask_out,
-                         int B, int S, int H, int W) {
+tgt_composite_fwd_kernel(const float* __restrict__ mpi,     // (Bm,S,H,W,4)
+                         const float* __restrict__ hinv,    // (R,S,3,3)
+                         const float* __restrict__ m_rki,   // (R,3,3)
+                         const float* __restrict__ tvec,    // (R,3)
+                         const float* __restrict__ depths,  // (Bm,S)
+                         float* __restrict__ rgb_out,       // (R,3,H,W)
+                         float* __restrict__ depth_out,     // (R,1,H,W)
+                         float* __restrict__ mask_out,      // (R,1,H,W)
+                         int Bm, int S, int H, int W) {
   __shared__ float s_geom[kMaxS * 9];
   __shared__ float s_depth[kMaxS];
+  // VIEW ROWS. The grid has R = gridDim.y rows. Row b takes its geometry
+  // and writes its outputs at index b; it reads the MPI and the plane
+  // depths of batch element b % Bm, Bm being the MPI batch count. Single
+  // view: R == Bm. View-batched: R = V * Bm rows, view-major, so V
+  // cameras read one MPI.
   const int b = blockIdx.y;
+  const int bm = b % Bm;
   for (int i = threadIdx.x; i < S * 9; i += kBlock) s_geom[i] = hinv[(int64_t)b * S * 9 + i];
-  for (int i = threadIdx.x; i < S; i += kBlock) s_depth[i] = depths[b * S + i];
+  for (int i = threadIdx.x; i < S; i += kBlock) s_depth[i] = depths[bm * S + i];
   __syncthreads();
 
   float3x3 M;
@@ -467,7 +473,7 @@ tgt_composite_fwd_kernel(const float* __restrict__ mpi,
   const float3 tv = make_float3(tvec[b * 3], tvec[b * 3 + 1], tvec[b * 3 + 2]);
 
   const int HW = H * W;
-  const float* mpi_b = mpi + (int64_t)b * S * HW * 4;
+  const float* mpi_b = mpi + (int64_t)bm * S * HW * 4;
   for (int pix = blockIdx.x * kBlock + threadIdx.x; pix < HW;
        pix += gridDim.x * kBlock) {
     const int y = pix / W;
@@ -956,6 +962,11 @@ tgt_gather_kernel(const float* __restrict__ payload,  // (B,S,H,W,4)
 // store, zeros included (grad_mpi needs no zero fill). The order is a
 // function of the shapes and the geometry alone.
 //
+// ACCUM is the form of the view-batched backward for every view after the
+// first: the owner's sum is formed exactly as above and then
+// grad_mpi = grad_mpi + sum in one plain read-add-write by the owner, so
+// V stream-ordered launches leave ((g_0 + g_1) + g_2) ... bit for bit.
+//
 // MEMBERSHIP is decided exactly as the scatter decides it: make_tap of
 // project_uv on the same hinv row (contraction rule); a tap contributes
 // if it equals (qx, qy) and its weight is non-zero. Nothing else
@@ -1007,6 +1018,7 @@ DEV void collect_tap(float4& acc, float w, float4 g) {
   acc.w = acc.w + w * g.w;
 }
 
+template <bool ACCUM>
 __global__ void __launch_bounds__(kBlock)
 tgt_collect_kernel(const float* __restrict__ payload,  // (B,S,H,W,4)
                    const float* __restrict__ hinv,     // (B,S,3,3) tgt->src
@@ -1115,13 +1127,34 @@ tgt_collect_kernel(const float* __restrict__ payload,  // (B,S,H,W,4)
         if (t.x1 == qx && t.y1 == qy && w11 != 0.0f) collect_tap(acc, w11, g);
       }
     }
-    *reinterpret_cast<float4*>(gm + (unsigned)q * 4u) = acc;
+    float4* dst = reinterpret_cast<float4*>(gm + (unsigned)q * 4u);
+    if (ACCUM) {
+      const float4 cur = *dst;
+      acc = make_float4(cur.x + acc.x, cur.y + acc.y, cur.z + acc.z,
+                        cur.w + acc.w);
+    }
+    *dst = acc;
   }
 }
 
 inline int grid_x(int HW) {
   int g = (HW + kBlock - 1) / kBlock;
   return g < 4096 ? g : 4096;
+}
+
+// accum false: grad_mpi = pull of `payload` (no fill needed); accum true:
+// grad_mpi, holding the earlier views, += pull
+void launch_collect(bool accum, const float* payload, const float* hinv,
+                    const float* hfwd, float* grad_mpi, int B, int S, int H,
+                    int W, hipStream_t stream) {
+  dim3 grid(grid_x(H * W), S, B);
+  if (accum) {
+    hipLaunchKernelGGL(tgt_collect_kernel<true>, grid, dim3(kBlock), 0, stream,
+                       payload, hinv, hfwd, grad_mpi, B, S, H, W);
+  } else {
+    hipLaunchKernelGGL(tgt_collect_kernel<false>, grid, dim3(kBlock), 0,
+                       stream, payload, hinv, hfwd, grad_mpi, B, S, H, W);
+  }
 }
 
 }  // namespace
@@ -1206,26 +1239,47 @@ void mine_tgt_composite_fwd(const float* mpi, const float* hinv,
   })
 }
 
+// V cameras, one MPI: the same kernel over V*B view rows (VIEW ROWS)
+void mine_tgt_views_fwd(const float* mpi, const float* hinv,
+                        const float* m_rki, const float* tvec,
+                        const float* depths, float* rgb_out, float* depth_out,
+                        float* mask_out, int V, int B, int S, int H, int W,
+                        int bg_inf, int alpha, hipStream_t stream) {
+  dim3 grid(grid_x(H * W), V * B);
+  if (alpha) {
+    hipLaunchKernelGGL((tgt_composite_fwd_kernel<false, true>), grid,
+                       dim3(kBlock), 0, stream, mpi, hinv, m_rki, tvec,
+                       depths, rgb_out, depth_out, mask_out, B, S, H, W);
+    return;
+  }
+  DISPATCH_BOOL(bg_inf, BG, {
+    hipLaunchKernelGGL((tgt_composite_fwd_kernel<BG>), grid, dim3(kBlock), 0,
+                       stream, mpi, hinv, m_rki, tvec, depths, rgb_out,
+                       depth_out, mask_out, B, S, H, W);
+  })
+}
+
 // collect pass alone: grad_mpi (no fill needed) = pull of `payload`
 void mine_tgt_collect(const float* payload, const float* hinv,
                       const float* hfwd, float* grad_mpi, int B, int S, int H,
                       int W, hipStream_t stream) {
-  dim3 grid(grid_x(H * W), S, B);
-  hipLaunchKernelGGL(tgt_collect_kernel, grid, dim3(kBlock), 0, stream,
-                     payload, hinv, hfwd, grad_mpi, B, S, H, W);
+  launch_collect(false, payload, hinv, hfwd, grad_mpi, B, S, H, W, stream);
 }
 
 // mode 0: scatter everywhere (round-1 path); mode 1: gather redesign
 // (payload + hfwd required; grad_mpi pre-zeroed, payload need not be);
 // mode 2: order-fixed emit + collect (payload + hfwd required; neither
 // buffer needs a fill, grad_mpi is stored by the collect pass alone).
-void mine_tgt_composite_bwd(const float* mpi, const float* hinv,
-                            const float* hfwd, const float* m_rki,
-                            const float* tvec, const float* depths,
-                            const float* g_rgb, const float* g_depth,
-                            float* grad_mpi, float* payload,
-                            int B, int S, int H, int W, int bg_inf, int mode,
-                            int alpha, hipStream_t stream) {
+//
+// `accum` (mode 2 only) selects the collect pass that adds to grad_mpi;
+// modes 0 and 1 add to grad_mpi in any case.
+static void tgt_bwd_one_view(const float* mpi, const float* hinv,
+                             const float* hfwd, const float* m_rki,
+                             const float* tvec, const float* depths,
+                             const float* g_rgb, const float* g_depth,
+                             float* grad_mpi, float* payload,
+                             int B, int S, int H, int W, int bg_inf, int mode,
+                             int alpha, bool accum, hipStream_t stream) {
   dim3 grid(grid_x(H * W), B);
 #define TGT_BWD_LAUNCH(BGv, MODEv, ALv, GM, PAY)                              \
   hipLaunchKernelGGL((tgt_composite_bwd_kernel<BGv, MODEv, ALv>), grid,       \
@@ -1234,7 +1288,7 @@ void mine_tgt_composite_bwd(const float* mpi, const float* hinv,
 #define TGT_BWD_BODY(BGv, ALv)                                                \
   if (mode == 2) {                                                            \
     TGT_BWD_LAUNCH(BGv, kTgtEmit, ALv, nullptr, payload);                     \
-    mine_tgt_collect(payload, hinv, hfwd, grad_mpi, B, S, H, W, stream);      \
+    launch_collect(accum, payload, hinv, hfwd, grad_mpi, B, S, H, W, stream); \
   } else if (mode == 1) {                                                     \
     TGT_BWD_LAUNCH(BGv, kTgtGather, ALv, grad_mpi, payload);                  \
     const int tiles_x = (W + GT - 1) / GT;                                    \
@@ -1252,6 +1306,40 @@ void mine_tgt_composite_bwd(const float* mpi, const float* hinv,
   DISPATCH_BOOL(bg_inf, BG, { TGT_BWD_BODY(BG, false) })
 #undef TGT_BWD_BODY
 #undef TGT_BWD_LAUNCH
+}
+
+void mine_tgt_composite_bwd(const float* mpi, const float* hinv,
+                            const float* hfwd, const float* m_rki,
+                            const float* tvec, const float* depths,
+                            const float* g_rgb, const float* g_depth,
+                            float* grad_mpi, float* payload,
+                            int B, int S, int H, int W, int bg_inf, int mode,
+                            int alpha, hipStream_t stream) {
+  tgt_bwd_one_view(mpi, hinv, hfwd, m_rki, tvec, depths, g_rgb, g_depth,
+                   grad_mpi, payload, B, S, H, W, bg_inf, mode, alpha, false,
+                   stream);
+}
+
+// View after view in stream order, each at its own offsets into the
+// view-major geometry and upstream gradients; ONE payload and ONE
+// grad_mpi serve all of them. Modes 0 and 1 add into the zero-filled
+// grad_mpi (atomics, and the gather flush's read-add-write); mode 2
+// stores view 0 and accumulates the later ones in ascending order.
+void mine_tgt_views_bwd(const float* mpi, const float* hinv, const float* hfwd,
+                        const float* m_rki, const float* tvec,
+                        const float* depths, const float* g_rgb,
+                        const float* g_depth, float* grad_mpi, float* payload,
+                        int V, int B, int S, int H, int W, int bg_inf,
+                        int mode, int alpha, hipStream_t stream) {
+  const int64_t HW = (int64_t)H * W;
+  for (int v = 0; v < V; ++v) {
+    const int64_t r = (int64_t)v * B;  // first view row
+    tgt_bwd_one_view(mpi, hinv + r * S * 9, hfwd ? hfwd + r * S * 9 : nullptr,
+                     m_rki + r * 9, tvec + r * 3, depths,
+                     g_rgb ? g_rgb + r * 3 * HW : nullptr,
+                     g_depth ? g_depth + r * HW : nullptr, grad_mpi, payload,
+                     B, S, H, W, bg_inf, mode, alpha, v > 0, stream);
+  }
 }
 
 }  // extern "C"

@@ -212,6 +212,104 @@ class _TgtCompositeFn(torch.autograd.Function):
         return grad_mpi, None, None, None, None, None, None
 
 
+class _TgtViewsFn(torch.autograd.Function):
+    """_TgtCompositeFn for V cameras that read ONE MPI.
+
+    inputs:  mpi (B,S,H,W,4), hinv (V,B,S,3,3), m (V,B,3,3), tvec (V,B,3),
+             depths (B,S)
+    outputs: tgt_rgb (V,B,3,H,W), tgt_depth (V,B,1,H,W), tgt_mask (V,B,1,H,W)
+
+    The forward is one launch of the single-view kernel over V*B view
+    rows. The backward leaves ONE grad_mpi through ONE MPI-sized payload,
+    view after view in stream order.
+    """
+
+    @staticmethod
+    def forward(ctx, mpi, hinv, m, tvec, depths, bg_inf, alpha):
+        ext = get_extension(required=True)
+        V = hinv.shape[0]
+        rgb, depth, mask = ext._views.tgt_views_fwd(
+            mpi, hinv, m, tvec, depths, V, bool(bg_inf), bool(alpha))
+        ctx.save_for_backward(mpi, hinv, m, tvec, depths)
+        ctx.bg_inf = bool(bg_inf)
+        ctx.alpha = bool(alpha)
+        # read once here, as _TgtCompositeFn does
+        ctx.det = is_deterministic()
+        return rgb, depth, mask
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth, g_mask):
+        mpi, hinv, m, tvec, depths = ctx.saved_tensors
+        ext = get_extension(required=True)
+        empty = torch.empty(0, device=mpi.device, dtype=torch.float32)
+        mode = 2 if ctx.det else tgt_bwd_mode()
+        if mode >= 1:
+            from mine_amd.utils.geometry import inverse_3x3
+            with torch.no_grad():
+                hfwd = inverse_3x3(hinv.reshape(-1, 3, 3)) \
+                    .reshape(hinv.shape).contiguous()
+        else:
+            hfwd = empty
+        grad_mpi = ext._views.tgt_views_bwd(
+            mpi, hinv, hfwd, m, tvec, depths, hinv.shape[0], ctx.bg_inf,
+            ctx.alpha,
+            g_rgb.contiguous() if g_rgb is not None else empty,
+            g_depth.contiguous() if g_depth is not None else empty,
+            mode)
+        return grad_mpi, None, None, None, None, None, None
+
+
+def render_tgt_views(mpi: torch.Tensor,
+                     disparity: torch.Tensor,
+                     G_tgt_src: torch.Tensor,
+                     K_src_inv: torch.Tensor,
+                     K_tgt: torch.Tensor,
+                     bg_depth_inf: bool = False,
+                     use_alpha: bool = False,
+                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Render ONE MPI into V novel views.
+
+    mpi (B,S,H,W,4), disparity (B,S) and K_src_inv (B,3,3) as in
+    render_tgt_view; G_tgt_src (V,B,4,4) and K_tgt (V,B,3,3) are
+    view-major. Returns (tgt_rgb (V,B,3,H,W), tgt_depth (V,B,1,H,W),
+    tgt_mask (V,B,1,H,W)): every [v] slice is what render_tgt_view gives
+    for view v, bit for bit on the GPU. Differentiable in mpi only; its
+    gradient is the sum over the views, accumulated in one MPI-sized
+    buffer (no per-view copy of the MPI or of its gradient).
+    """
+    V, B = G_tgt_src.shape[0], mpi.shape[0]
+    if G_tgt_src.dim() != 4 or G_tgt_src.shape[1] != B \
+            or K_tgt.shape[:2] != G_tgt_src.shape[:2]:
+        raise ValueError(
+            "render_tgt_views: G_tgt_src must be (V,B,4,4) and K_tgt "
+            f"(V,B,3,3) with B = {B}, got {tuple(G_tgt_src.shape)} and "
+            f"{tuple(K_tgt.shape)}")
+    if mpi.is_cuda:
+        depths = torch.reciprocal(disparity).to(torch.float32)
+        with torch.no_grad():
+            # all V*B*S planes in one batched call
+            G = G_tgt_src.reshape(V * B, 4, 4)
+            K_si = K_src_inv.repeat(V, 1, 1)
+            hinv = tr.homography_tgt_to_src(
+                G, depths.repeat(V, 1), K_si, K_tgt.reshape(V * B, 3, 3))
+            S = depths.shape[1]
+            hinv = hinv.reshape(V, B, S, 3, 3).contiguous()
+            m = torch.matmul(G[:, :3, :3], K_si).reshape(V, B, 3, 3) \
+                .contiguous()
+            tvec = G[:, :3, 3].reshape(V, B, 3).contiguous()
+        return _TgtViewsFn.apply(mpi.contiguous(), hinv, m, tvec,
+                                 depths.contiguous(), bg_depth_inf, use_alpha)
+
+    rgb, sigma = unpack_mpi(mpi)
+    if V == 0:
+        raise ValueError("render_tgt_views: needs at least one view")
+    outs = [tr.render_tgt_reference(rgb, sigma, disparity, G_tgt_src[v],
+                                    K_src_inv, K_tgt[v], use_alpha=use_alpha,
+                                    bg_depth_inf=bg_depth_inf)
+            for v in range(V)]
+    return tuple(torch.stack(o, dim=0) for o in zip(*outs))
+
+
 def render_tgt_view(mpi: torch.Tensor,
                     disparity: torch.Tensor,
                     G_tgt_src: torch.Tensor,

@@ -4,7 +4,7 @@ four scales, as effective bandwidth.
 
     python tools/render_bench.py [--root OTHER_CHECKOUT] [--reps 9]
                                  [--scales 0,1,2,3] [--only {all,fwd,bwd}]
-                                 [--no-split] [--mode {1,2}]
+                                 [--no-split] [--mode {1,2}] [--views V]
 
 B = 4, S = 64, fp32 MPI (B,S,H,W,4) at 256x384, 128x192, 64x96, 32x48.
 Seeded inputs: small camera motion, and sigma small enough that the
@@ -28,6 +28,12 @@ write) reaches on a tensor of N bytes in the same process.
 the emit instance of the backward kernel, `tgt_collect_kernel` in the
 gather kernel's place, and no fill at all.
 
+--views V times the view-batched op instead (V cameras on a small circle
+around the scene's pose, all reading the one MPI): `tgt_views_fwd` and
+`tgt_views_bwd` in --mode, each against V calls of the single-view
+binding on the same geometry, and the peak memory either backward
+allocates on top of its inputs.
+
 --root imports mine_amd from another built checkout, so two builds can be
 timed with the same scenes. --only and --scales narrow the run to a few
 dispatches for a counter collection.
@@ -41,6 +47,7 @@ ap.add_argument("--scales", default="0,1,2,3")
 ap.add_argument("--only", choices=("all", "fwd", "bwd"), default="all")
 ap.add_argument("--no-split", action="store_true")
 ap.add_argument("--mode", type=int, choices=(1, 2), default=1)
+ap.add_argument("--views", type=int, default=0)
 args = ap.parse_args()
 sys.path.insert(0, args.root)
 import torch
@@ -113,6 +120,100 @@ def scene(H, W, seed):
     g_rgb = torch.randn(B, 3, H, W, generator=g).to(DEV)
     g_depth = torch.randn(B, 1, H, W, generator=g).to(DEV)
     return mpi, depths, hinv, hfwd, m, tvec, g_rgb, g_depth
+
+
+def views_scene(H, W, seed, V):
+    """scene() plus V view-major poses: the scene's pose moved along a small
+    circle (radius 0.03), as neighbouring frames of a video trajectory."""
+    import math
+    mpi, depths, hinv0, _, _, _, _, _ = scene(H, W, seed)
+    g = torch.Generator().manual_seed(seed + 50)
+    f = 0.8 * W
+    K = torch.tensor([[f, 0.0, W / 2], [0.0, f, H / 2], [0.0, 0.0, 1.0]])
+    K = K.unsqueeze(0).repeat(B, 1, 1).to(DEV)
+    K_inv = torch.inverse(K)
+    G = torch.eye(4).repeat(V, B, 1, 1)
+    for v in range(V):
+        a = 2.0 * math.pi * v / V
+        G[v, :, 0, 3] = 0.03 * math.sin(a)
+        G[v, :, 1, 3] = 0.03 * math.cos(a)
+        G[v, :, 2, 3] = 0.02 * v / V
+    G = G.to(DEV).reshape(V * B, 4, 4)
+    K_si = K_inv.repeat(V, 1, 1)
+    hinv = tr.homography_tgt_to_src(G, depths.repeat(V, 1), K_si,
+                                    K.repeat(V, 1, 1))
+    hfwd = inverse_3x3(hinv.reshape(-1, 3, 3))
+    shape = lambda t, *tail: t.reshape(V, B, *tail).contiguous()
+    g_rgb = torch.randn(V, B, 3, H, W, generator=g).to(DEV)
+    g_depth = torch.randn(V, B, 1, H, W, generator=g).to(DEV)
+    return (mpi, depths, shape(hinv, S, 3, 3), shape(hfwd, S, 3, 3),
+            shape(torch.matmul(G[:, :3, :3], K_si), 3, 3),
+            shape(G[:, :3, 3], 3), g_rgb, g_depth)
+
+
+def peak_extra(fn):
+    """Peak bytes `fn` allocates on top of what is live before it."""
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    out = fn()
+    torch.cuda.synchronize()
+    del out
+    return torch.cuda.max_memory_allocated() - base
+
+
+def run_views(V):
+    print(f"root {args.root}")
+    print(f"view-batched op against {V} single-view calls, backward mode "
+          f"{args.mode}")
+    print(f"{'HxW':>9} {'N MB':>6} | {'what':<10} {'views ms':>9} "
+          f"{'single ms':>9} {'ratio':>6} | peak extra MB: views, single")
+    for si in [int(v) for v in args.scales.split(",")]:
+        H, W = SCALES[si]
+        mpi, depths, hinv, hfwd, m, tvec, g_rgb, g_depth = \
+            views_scene(H, W, 100 + si, V)
+        N = mpi.numel() * 4
+        vb = ext._views
+
+        def fwd_v():
+            return vb.tgt_views_fwd(mpi, hinv, m, tvec, depths, V, False,
+                                    False)
+
+        def fwd_1():
+            return [ext.tgt_composite_fwd(mpi, hinv[v], m[v], tvec[v],
+                                          depths, False, False)
+                    for v in range(V)]
+
+        def bwd_v():
+            return vb.tgt_views_bwd(mpi, hinv, hfwd, m, tvec, depths, V,
+                                    False, False, g_rgb, g_depth, args.mode)
+
+        def bwd_1():
+            # what autograd does with V single-view ops: V gradients of the
+            # size of the MPI, summed
+            total = None
+            for v in range(V):
+                g = ext.tgt_composite_bwd(mpi, hinv[v], hfwd[v], m[v],
+                                          tvec[v], depths, False, False,
+                                          g_rgb[v], g_depth[v], args.mode)
+                total = g if total is None else total.add_(g)
+            return total
+
+        with torch.no_grad():
+            for what, fv, f1 in (("fwd", fwd_v, fwd_1), ("bwd", bwd_v, bwd_1)):
+                if args.only not in ("all", what):
+                    continue
+                tv, t1 = tm(fv, args.reps), tm(f1, args.reps)
+                pv, p1 = peak_extra(fv), peak_extra(f1)
+                print(f"{H:>4}x{W:<4} {N / 1e6:6.1f} | {what:<10} {tv:9.3f} "
+                      f"{t1:9.3f} {tv / t1:6.2f} | {pv / 1e6:8.1f} "
+                      f"{p1 / 1e6:8.1f}")
+        del mpi
+
+
+if args.views > 0:
+    run_views(args.views)
+    sys.exit(0)
 
 
 def kernel_split(fn, reps):

@@ -7,12 +7,15 @@ CLI contract follows the reference (ref visualizations/image_to_video.py:259-265
         --checkpoint_path /ws/checkpoint.pth [--data_path img_or_scene] \
         --output_dir /out [--gpus 0] [--extra_config '{...}'] \
         [--traj circle|straight-line|double-straight-line] \
-        [--benchmark] [--num_frames 90]
+        [--benchmark] [--num_frames 90] [--views 16]
 
 Reads ``params.yaml`` sitting next to the checkpoint (the checkpoint-dir
 contract, ref image_to_video.py:272-278), computes the MPI ONCE from the
-source image, then renders a camera trajectory by per-frame homography
-warp + composite of the cached MPI (ref image_to_video.py:90-255).
+source image, then renders a camera trajectory by homography warp +
+composite of the cached MPI (ref image_to_video.py:90-255). The frames
+are rendered ``--views`` at a time: that many cameras read the MPI in one
+launch (ops.render_tgt_views) and come back in one device-to-host copy.
+``--views 1`` is the per-frame loop; the frames are the same bytes.
 
 Output: ``frames/%05d.png`` + ``video.mp4`` when ffmpeg is on PATH
 (moviepy/cv2 are not in this environment). ``--benchmark`` times the
@@ -154,20 +157,49 @@ class VideoGenerator:
             self.mpi, self.disparity, G, self.K_inv, self.K)
 
     @torch.no_grad()
-    def render_video(self, offsets, out_dir: str, save_depth: bool = False):
+    def render_poses(self, offsets) -> dict:
+        """Render the cached MPI at V camera offsets at once: the V
+        cameras read the one MPI in one launch. Outputs are (V, ...)."""
+        V = len(offsets)
+        G = torch.eye(4, device=self.device).repeat(V, 1, 1)
+        G[:, 0:3, 3] = torch.as_tensor(
+            np.asarray(offsets), dtype=torch.float32).to(self.device)
+        return self.task.render_novel_view(
+            self.mpi, self.disparity, G, self.K_inv, self.K.repeat(V, 1, 1))
+
+    @torch.no_grad()
+    def render_video(self, offsets, out_dir: str, save_depth: bool = False,
+                     views: int = 16):
+        """Write frames/%05d.png (+ video.mp4). `views` poses are rendered
+        per launch and copied to the host together (the disparity maps,
+        if asked for, in a copy of their own); views=1 is the per-frame
+        loop. The frames do not depend on `views`."""
         from PIL import Image as PILImage
         frames_dir = os.path.join(out_dir, "frames")
         os.makedirs(frames_dir, exist_ok=True)
-        for i, off in enumerate(offsets):
-            res = self.render_pose(off)
-            rgb = res["tgt_imgs_syn"][0].clamp(0, 1)
-            arr = (rgb.permute(1, 2, 0).float().cpu().numpy() * 255).astype(np.uint8)
-            PILImage.fromarray(arr).save(
-                os.path.join(frames_dir, "%05d.png" % i))
-            if save_depth:
-                PILImage.fromarray(
-                    disparity_colormap(res["tgt_disparity_syn"][0])).save(
-                    os.path.join(frames_dir, "disp_%05d.png" % i))
+        if views <= 1:
+            for i, off in enumerate(offsets):
+                res = self.render_pose(off)
+                rgb = res["tgt_imgs_syn"][0].clamp(0, 1)
+                arr = (rgb.permute(1, 2, 0).float().cpu().numpy() * 255).astype(np.uint8)
+                PILImage.fromarray(arr).save(
+                    os.path.join(frames_dir, "%05d.png" % i))
+                if save_depth:
+                    PILImage.fromarray(
+                        disparity_colormap(res["tgt_disparity_syn"][0])).save(
+                        os.path.join(frames_dir, "disp_%05d.png" % i))
+        else:
+            for i0 in range(0, len(offsets), views):
+                res = self.render_poses(offsets[i0:i0 + views])
+                rgb = res["tgt_imgs_syn"].clamp(0, 1)
+                arr = (rgb.permute(0, 2, 3, 1).float().cpu().numpy() * 255).astype(np.uint8)
+                disp = res["tgt_disparity_syn"].cpu() if save_depth else None
+                for k in range(arr.shape[0]):
+                    PILImage.fromarray(arr[k]).save(
+                        os.path.join(frames_dir, "%05d.png" % (i0 + k)))
+                    if save_depth:
+                        PILImage.fromarray(disparity_colormap(disp[k])).save(
+                            os.path.join(frames_dir, "disp_%05d.png" % (i0 + k)))
         self._encode(frames_dir, os.path.join(out_dir, "video.mp4"))
 
     @staticmethod
@@ -184,8 +216,9 @@ class VideoGenerator:
 
     @torch.no_grad()
     def benchmark_fps(self, offsets, warmup: int = 10,
-                      use_graph: bool = False) -> float:
-        """Sync-bracketed per-frame render timing -> FPS.
+                      use_graph: bool = False, views: int = 1) -> float:
+        """Sync-bracketed render timing -> FPS, `views` frames per launch
+        (the graph replay is per frame and ignores `views`).
 
         With ``use_graph`` the whole per-frame render (homography build,
         closed-form inverses, fused warp+composite) is captured once into
@@ -215,6 +248,20 @@ class VideoGenerator:
                 pose[0, 0:3, 3] = poses[i]
                 graph.replay()
             torch.cuda.synchronize()
+            return len(offsets) / (time.perf_counter() - t0)
+
+        if views > 1:
+            chunks = [offsets[i:i + views]
+                      for i in range(0, len(offsets), views)]
+            for c in chunks[:max(1, warmup // views)]:
+                self.render_poses(c)
+            if is_gpu:
+                torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for c in chunks:
+                self.render_poses(c)
+            if is_gpu:
+                torch.cuda.synchronize()
             return len(offsets) / (time.perf_counter() - t0)
 
         for off in offsets[:warmup]:
@@ -261,6 +308,9 @@ def main() -> int:
                    help="time per-frame novel-view render, print JSON FPS line")
     p.add_argument("--graph", action="store_true",
                    help="capture the per-frame render in a hipGraph and replay")
+    p.add_argument("--views", type=int, default=16,
+                   help="frames rendered per launch from the cached MPI "
+                        "(1 = the per-frame loop)")
     p.add_argument("--save_depth", action="store_true")
     args = p.parse_args()
 
@@ -293,12 +343,14 @@ def main() -> int:
     offsets = path_planning(args.traj, frames=args.num_frames, **preset)
 
     if args.benchmark:
-        fps = gen.benchmark_fps(offsets, use_graph=args.graph)
+        views = 1 if args.graph else max(1, args.views)
+        fps = gen.benchmark_fps(offsets, use_graph=args.graph, views=views)
         print(json.dumps({
             "metric": "novel-view render FPS",
             "value": round(fps, 2), "unit": "frames/sec",
             "n_gpus": 1, "higher_is_better": True,
             "hipgraph": bool(args.graph),
+            "views": views,
             "config": {"img_h": H, "img_w": W,
                        "n_planes": int(gen.disparity.shape[1]),
                        "dataset": cfg["data.name"]},
@@ -306,7 +358,8 @@ def main() -> int:
         return 0
 
     os.makedirs(args.output_dir, exist_ok=True)
-    gen.render_video(offsets, args.output_dir, save_depth=args.save_depth)
+    gen.render_video(offsets, args.output_dir, save_depth=args.save_depth,
+                     views=max(1, args.views))
     return 0
 
 
