@@ -12,10 +12,19 @@ nn.BatchNorm2d so parameter/buffer names (weight, bias, running_mean,
 running_var, num_batches_tracked) — and therefore the checkpoint
 contract — are unchanged (ref CS5).
 
+Small layers (the batch-4 encoder and neck; `ext._bn.small_plan`) take a
+two-launch path per direction: a reduction into a few partial rows and a
+consumer that finishes the sum in its prologue and also does the finalize,
+the running-statistics update and the batch count. It is order-fixed, so
+it serves the default and the deterministic mode alike; MINE_BN_COMPACT=0
+turns it off.
+
 Fallback paths (CPU, non-channels_last, exotic dtype, eval-with-grad):
 fp32 functional BN + eager activation, numerically equivalent.
 """
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.nn as nn
@@ -63,6 +72,54 @@ class _BNActFn(torch.autograd.Function):
                                      gamma, beta, red, M, C, act, M_norm)
         return (dx, dres if act == _ACT["add_relu"] else None, None, None,
                 dgamma, dbeta, None, None, None, None)
+
+
+def compact_enabled() -> bool:
+    """MINE_BN_COMPACT=0 keeps every layer on the four-launch path (A/B in
+    one build); read per call, so a test can flip it."""
+    return os.environ.get("MINE_BN_COMPACT", "1") != "0"
+
+
+_PLAN = {}
+
+
+def _plan_says_small(ext, M: int, C: int, dtype) -> bool:
+    key = (M, C, dtype)
+    if key not in _PLAN:
+        _PLAN[key] = bool(ext._bn.small_plan(M, C, dtype)[0])
+    return _PLAN[key]
+
+
+class _BNActSmallFn(torch.autograd.Function):
+    """The small-layer path (bn_kernels.hip): per direction one reduction
+    into a few partial rows and one consumer that finishes the sum itself.
+    The forward consumer also stores mean / invstd, updates the running
+    statistics and increments num_batches_tracked — `bufs`, a plain tuple,
+    so autograd does not see the buffers."""
+
+    @staticmethod
+    def forward(ctx, x_flat, res_flat, gamma, beta, bufs, M, C, act, eps,
+                mom):
+        bn = get_extension(required=True)._bn
+        ws = bn.stats_partials(x_flat, M, C)
+        y, mean, invstd = bn.act_fwd_ws(x_flat, res_flat, ws, gamma, beta, M,
+                                        C, act, *bufs, eps, mom)
+        ctx.save_for_backward(x_flat, res_flat, mean, invstd, gamma, beta)
+        ctx.geom = (M, C, act)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        bn = get_extension(required=True)._bn
+        x_flat, res_flat, mean, invstd, gamma, beta = ctx.saved_tensors
+        M, C, act = ctx.geom
+        gy = gy.contiguous()
+        ws = bn.bwd_reduce_partials(x_flat, res_flat, gy, mean, invstd, gamma,
+                                    beta, M, C, act)
+        dx, dres, red = bn.act_bwd_dx_ws(x_flat, res_flat, gy, mean, invstd,
+                                         gamma, beta, ws, M, C, act)
+        return (dx, dres if act == _ACT["add_relu"] else None, red[C:],
+                red[:C], None, None, None, None, None, None)
 
 
 class _JoinStatsFn(torch.autograd.Function):
@@ -180,6 +237,21 @@ class FusedBNAct(nn.BatchNorm2d):
         do_sync = self.training and self.sync and \
             torch.distributed.is_initialized() and \
             torch.distributed.get_world_size() > 1
+        if (self.training and not do_sync and sums is None
+                and self.momentum is not None and compact_enabled()
+                and _plan_says_small(ext, M, C, x.dtype)):
+            # two launches per direction; the forward consumer does the
+            # finalize, the running update and the batch count
+            empty = torch.empty(0, device=x.device, dtype=torch.float32)
+            track = self.track_running_stats and self.running_mean is not None
+            nbt = self.num_batches_tracked
+            bufs = (self.running_mean if track else empty,
+                    self.running_var if track else empty,
+                    nbt if nbt is not None else empty)
+            y = _BNActSmallFn.apply(
+                x_flat, res_flat, self.weight.float(), self.bias.float(),
+                bufs, M, C, _ACT[self.act], self.eps, self.momentum)
+            return y.view(B, H, W, C).permute(0, 3, 1, 2)
         if self.training:
             if self.num_batches_tracked is not None:
                 self.num_batches_tracked.add_(1)

@@ -744,6 +744,144 @@ std::vector<at::Tensor> bn_act_bwd(at::Tensor x, at::Tensor res,
   return {dxr[0], dxr[1], red.narrow(0, C, C), red.narrow(0, 0, C)};
 }
 
+// Small-layer path (submodule _bn; bn_kernels.hip): a reduction stores G
+// partials into a workspace (G,2,C) and the consumer adds them itself, so
+// a direction is two launches with no fill, finish or counter launch.
+// max_blocks > 0 forces the reduction's G, or the consumer's grid.x, in
+// place of the plan's; a consumer names the G of its workspace the same
+// way (max_blocks_reduce).
+struct BnSmall {
+  bool small;
+  int G, cgv, grid_x;
+};
+
+BnSmall bn_small(const char* who, const at::Tensor& x, int64_t M, int64_t C,
+                 int64_t max_blocks_reduce, int64_t max_blocks, int64_t cgv) {
+  for (const int64_t v : {max_blocks_reduce, max_blocks})
+    TORCH_CHECK(v >= 0 && v <= 4096, who, ": max_blocks out of range");
+  BnSmall p{};
+  const int rc = mine_bn_small_plan(M, (int)C, elem_of(x.scalar_type(), who),
+                                    &p.G, &p.cgv, &p.grid_x);
+  TORCH_CHECK(rc >= 0, who, ": no plan for this dtype");
+  p.small = rc == 1;
+  if (max_blocks_reduce > 0) p.G = (int)max_blocks_reduce;
+  if (max_blocks > 0) p.grid_x = (int)max_blocks;
+  if (cgv > 0) {
+    TORCH_CHECK(cgv <= 64 && (cgv & (cgv - 1)) == 0, who,
+                ": cgv must be a power of two up to 64");
+    p.cgv = (int)cgv;
+  }
+  return p;
+}
+
+// (small, G, reduction cgv, consumer grid.x) for (M, C) of `dtype`
+std::tuple<bool, int64_t, int64_t, int64_t> bn_small_plan(
+    int64_t M, int64_t C, at::ScalarType dtype) {
+  const char* who = "small_plan";
+  check_ints(who, {M, C});
+  int G, cgv, grid_x;
+  const int rc = mine_bn_small_plan(M, (int)C, elem_of(dtype, who), &G, &cgv,
+                                    &grid_x);
+  return {rc == 1, G, cgv, grid_x};
+}
+
+at::Tensor bn_stats_partials(at::Tensor x, int64_t M, int64_t C,
+                             int64_t max_blocks, int64_t cgv) {
+  const char* who = "stats_partials";
+  check_bn_x(who, x, M, C, max_blocks);
+  const BnSmall p = bn_small(who, x, M, C, max_blocks, 0, cgv);
+  auto ws = at::empty({p.G, 2, C}, x.options().dtype(at::kFloat));
+  launched(who, mine_bn_stats_partials(x.data_ptr(), ws.data_ptr<float>(), M,
+                                       (int)C, p.G, p.cgv,
+                                       elem_of(x.scalar_type(), who),
+                                       stream()));
+  return ws;
+}
+
+// -> y, mean, invstd; running_mean / running_var / num_batches_tracked are
+// updated in place where given
+std::vector<at::Tensor> bn_act_fwd_ws(
+    at::Tensor x, at::Tensor res, at::Tensor ws, at::Tensor gamma,
+    at::Tensor beta, int64_t M, int64_t C, int64_t act,
+    at::Tensor running_mean, at::Tensor running_var,
+    at::Tensor num_batches_tracked, double eps, double momentum,
+    int64_t max_blocks_reduce, int64_t max_blocks) {
+  const char* who = "act_fwd_ws";
+  check_bn_x(who, x, M, C, max_blocks);
+  const void* res_p = opt_arg<const void>(
+      who, "res", res, x, dtype_bit(x.scalar_type()), M * C);
+  const BnSmall p = bn_small(who, x, M, C, max_blocks_reduce, max_blocks, 0);
+  check_arg(who, "ws", ws, x, kF32, (int64_t)p.G * 2 * C);
+  check_arg(who, "gamma", gamma, x, kF32, C);
+  check_arg(who, "beta", beta, x, kF32, C);
+  TORCH_CHECK(act >= 0 && act <= 4, who, ": unknown activation");
+  TORCH_CHECK(act != 4 || res_p != nullptr, who,
+              ": res is required for add_relu");
+  float *rm, *rv;
+  check_running(who, x, running_mean, running_var, C, &rm, &rv);
+  int64_t* nbt = opt_arg<int64_t>(who, "num_batches_tracked",
+                                  num_batches_tracked, x, kI64, 1);
+  const auto fopt = x.options().dtype(at::kFloat);
+  auto y = at::empty_like(x);
+  auto mean = at::empty({C}, fopt);
+  auto invstd = at::empty({C}, fopt);
+  launched(who, mine_bn_act_fwd_ws(
+                    x.data_ptr(), act == 4 ? res_p : nullptr,
+                    ws.data_ptr<float>(), p.G, gamma.data_ptr<float>(),
+                    beta.data_ptr<float>(), y.data_ptr(),
+                    mean.data_ptr<float>(), invstd.data_ptr<float>(), rm, rv,
+                    nbt, M, (int)C, (int)act, p.grid_x, (float)eps,
+                    (float)momentum, elem_of(x.scalar_type(), who), stream()));
+  return {y, mean, invstd};
+}
+
+at::Tensor bn_bwd_reduce_partials(at::Tensor x, at::Tensor res, at::Tensor gy,
+                                  at::Tensor mean, at::Tensor invstd,
+                                  at::Tensor gamma, at::Tensor beta, int64_t M,
+                                  int64_t C, int64_t act, int64_t max_blocks,
+                                  int64_t cgv) {
+  const char* who = "bwd_reduce_partials";
+  const void* res_p = check_bn_act(who, x, res, mean, invstd, gamma, beta, M,
+                                   C, act, max_blocks);
+  check_arg(who, "gy", gy, x, dtype_bit(x.scalar_type()), M * C);
+  const BnSmall p = bn_small(who, x, M, C, max_blocks, 0, cgv);
+  auto ws = at::empty({p.G, 2, C}, x.options().dtype(at::kFloat));
+  launched(who, mine_bn_act_bwd_reduce_partials(
+                    x.data_ptr(), act == 4 ? res_p : nullptr, gy.data_ptr(),
+                    mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                    gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                    ws.data_ptr<float>(), M, (int)C, (int)act, p.G, p.cgv,
+                    elem_of(x.scalar_type(), who), stream()));
+  return ws;
+}
+
+// -> dx, dres, red (2,C) = (dbeta, dgamma)
+std::vector<at::Tensor> bn_act_bwd_dx_ws(
+    at::Tensor x, at::Tensor res, at::Tensor gy, at::Tensor mean,
+    at::Tensor invstd, at::Tensor gamma, at::Tensor beta, at::Tensor ws,
+    int64_t M, int64_t C, int64_t act, int64_t max_blocks_reduce,
+    int64_t max_blocks) {
+  const char* who = "act_bwd_dx_ws";
+  const void* res_p = check_bn_act(who, x, res, mean, invstd, gamma, beta, M,
+                                   C, act, max_blocks);
+  check_arg(who, "gy", gy, x, dtype_bit(x.scalar_type()), M * C);
+  const BnSmall p = bn_small(who, x, M, C, max_blocks_reduce, max_blocks, 0);
+  check_arg(who, "ws", ws, x, kF32, (int64_t)p.G * 2 * C);
+  const bool add_relu = act == 4;
+  auto dx = at::empty_like(x);
+  auto dres = add_relu ? at::empty_like(x) : at::empty({0}, x.options());
+  auto red = at::empty({2 * C}, x.options().dtype(at::kFloat));
+  launched(who, mine_bn_act_bwd_dx_ws(
+                    x.data_ptr(), add_relu ? res_p : nullptr, gy.data_ptr(),
+                    mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                    gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                    ws.data_ptr<float>(), p.G, red.data_ptr<float>(),
+                    dx.data_ptr(), add_relu ? dres.data_ptr() : nullptr, M,
+                    (int)C, (int)act, p.grid_x, elem_of(x.scalar_type(), who),
+                    stream()));
+  return {dx, dres, red};
+}
+
 // --------------------------------------------------------------------------
 // fused MPI head (head_kernels.hip) over a flat (N,4) view of f32, bf16 or
 // fp16; the packed MPI is f32 (N,4)
@@ -1223,6 +1361,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("gy"), py::arg("mean"), py::arg("invstd"), py::arg("gamma"),
           py::arg("beta"), py::arg("red"), py::arg("M"), py::arg("C"),
           py::arg("act"), py::arg("M_norm"), py::arg("max_blocks") = 0);
+  // The small-layer BN path sits in a submodule, as _views does; its
+  // refusal table is in tests/test_bn_small_gpu.py.
+  auto bn = mod.def_submodule(
+      "_bn", "two-launch BatchNorm for small layers: partials + consumer");
+  bn.def("small_plan", &bn_small_plan,
+         "(small, G, reduction cgv, consumer grid.x) for (M, C) of dtype",
+         py::arg("M"), py::arg("C"), py::arg("dtype"));
+  bn.def("stats_partials", &bn_stats_partials, py::arg("x"), py::arg("M"),
+         py::arg("C"), py::arg("max_blocks") = 0, py::arg("cgv") = 0);
+  bn.def("act_fwd_ws", &bn_act_fwd_ws, py::arg("x"), py::arg("res"),
+         py::arg("ws"), py::arg("gamma"), py::arg("beta"), py::arg("M"),
+         py::arg("C"), py::arg("act"), py::arg("running_mean"),
+         py::arg("running_var"), py::arg("num_batches_tracked"),
+         py::arg("eps"), py::arg("momentum"),
+         py::arg("max_blocks_reduce") = 0, py::arg("max_blocks") = 0);
+  bn.def("bwd_reduce_partials", &bn_bwd_reduce_partials, py::arg("x"),
+         py::arg("res"), py::arg("gy"), py::arg("mean"), py::arg("invstd"),
+         py::arg("gamma"), py::arg("beta"), py::arg("M"), py::arg("C"),
+         py::arg("act"), py::arg("max_blocks") = 0, py::arg("cgv") = 0);
+  bn.def("act_bwd_dx_ws", &bn_act_bwd_dx_ws, py::arg("x"), py::arg("res"),
+         py::arg("gy"), py::arg("mean"), py::arg("invstd"), py::arg("gamma"),
+         py::arg("beta"), py::arg("ws"), py::arg("M"), py::arg("C"),
+         py::arg("act"), py::arg("max_blocks_reduce") = 0,
+         py::arg("max_blocks") = 0);
   mod.def("mpi_head_fwd", &mpi_head_fwd,
           "dispconv out -> packed fp32 MPI (sigmoid rgb, |x|+1e-4 sigma)");
   mod.def("mpi_head_bwd", &mpi_head_bwd);

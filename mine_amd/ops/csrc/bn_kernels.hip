@@ -30,6 +30,23 @@
 // result with plain stores into a workspace [gridDim.x][2][C].
 // bn_det_finish_kernel then adds the gridDim.x partials per channel in a
 // fixed order (see its comment) and optionally finalizes.
+//
+// Small-layer path (small_plan below; both modes): two launches per
+// direction, no zero fill, no global atomic, no finalize or counter
+// launch. The DET reductions run on a grid chosen by work — few partial
+// rows G, many rows per thread, U loads in flight — and store G partials
+// [G][2][C]; the WS instantiations of the normalize and dx kernels add
+// them in a prologue. Summation order, depending on (M, C, G, cgv) only:
+//   thread:   its rows in ascending order (the unrolled body issues its
+//             loads first and adds in row order);
+//   block:    the kBlock/cgv rows-in-block in ascending order
+//             (det_block_flush);
+//   partials: ascending g (ws_sum), by every consumer workgroup for its
+//             own channels, so all workgroups obtain the same bits.
+// Single owner: the workgroups with blockIdx.x == 0 alone store mean /
+// invstd (forward) or the (2, C) sums (backward) and update the running
+// statistics; thread 0 of block (0, 0) increments num_batches_tracked.
+// Data crosses workgroups only at the kernel boundary.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -201,7 +218,9 @@ __device__ __forceinline__ void bn_reduce(int C, int cgv,
 }
 
 // stats: per-channel sum and sum-of-squares
-template <typename T, int V, bool DET>
+// U > 1 (the small-layer path): U rows in flight, loads first, adds after
+// in row order — the sums are those of U = 1.
+template <typename T, int V, bool DET, int U = 1>
 __global__ void __launch_bounds__(kBlock)
 bn_stats_vec_kernel(const void* __restrict__ x, float* __restrict__ sums,
                     int64_t M, int C, int cgv) {
@@ -211,7 +230,25 @@ bn_stats_vec_kernel(const void* __restrict__ x, float* __restrict__ sums,
         const int Cv = C / V;
         const Vec* xv = static_cast<const Vec*>(x);
         const int rstride = lm.rstride();
-        for (int64_t m = lm.row0(); m < M; m += rstride) {
+        int64_t m = lm.row0();
+        if constexpr (U > 1) {
+          for (; m + (int64_t)(U - 1) * rstride < M; m += (int64_t)U * rstride) {
+            Vec val[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+              val[u] = xv[(m + (int64_t)u * rstride) * Cv + lm.col()];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#pragma unroll
+              for (int j = 0; j < V; ++j) {
+                const float f = (float)val[u].v[j];
+                acc[j] += f;
+                asq[j] += f * f;
+              }
+            }
+          }
+        }
+        for (; m < M; m += rstride) {
           const Vec val = xv[m * Cv + lm.col()];
 #pragma unroll
           for (int j = 0; j < V; ++j) {
@@ -223,21 +260,41 @@ bn_stats_vec_kernel(const void* __restrict__ x, float* __restrict__ sums,
       });
 }
 
-// mean/invstd of one channel from its sums; updates the running stats
+// mean, biased variance and invstd of one channel from its sums: the one
+// formula behind bn_finalize, the deterministic finish and the small-layer
+// forward, so equal sums give equal bits in all three
+struct BnMoments {
+  float mu, var, invstd;
+};
+__device__ __forceinline__ BnMoments bn_moments(float sum, float sumsq,
+                                                int64_t M, float eps) {
+  const float mu = sum / (float)M;
+  float var = sumsq / (float)M - mu * mu;
+  var = var > 0.0f ? var : 0.0f;
+  return {mu, var, rsqrtf(var + eps)};
+}
+
+// stores mean/invstd of channel c; updates the running stats where given
+__device__ __forceinline__ void bn_store_channel(
+    const BnMoments& mo, int c, float* __restrict__ mean,
+    float* __restrict__ invstd, float* __restrict__ running_mean,
+    float* __restrict__ running_var, int64_t M, float momentum) {
+  mean[c] = mo.mu;
+  invstd[c] = mo.invstd;
+  if (running_mean) {
+    running_mean[c] += momentum * (mo.mu - running_mean[c]);
+    const float unbiased =
+        M > 1 ? mo.var * (float)M / (float)(M - 1) : mo.var;
+    running_var[c] += momentum * (unbiased - running_var[c]);
+  }
+}
+
 __device__ __forceinline__ void bn_finalize_channel(
     float sum, float sumsq, int c, float* __restrict__ mean,
     float* __restrict__ invstd, float* __restrict__ running_mean,
     float* __restrict__ running_var, int64_t M, float eps, float momentum) {
-  const float mu = sum / (float)M;
-  float var = sumsq / (float)M - mu * mu;
-  var = var > 0.0f ? var : 0.0f;
-  mean[c] = mu;
-  invstd[c] = rsqrtf(var + eps);
-  if (running_mean) {
-    running_mean[c] += momentum * (mu - running_mean[c]);
-    const float unbiased = M > 1 ? var * (float)M / (float)(M - 1) : var;
-    running_var[c] += momentum * (unbiased - running_var[c]);
-  }
+  bn_store_channel(bn_moments(sum, sumsq, M, eps), c, mean, invstd,
+                   running_mean, running_var, M, momentum);
 }
 
 __global__ void bn_finalize_kernel(const float* __restrict__ sums,
@@ -323,7 +380,8 @@ bn_det_finish_kernel(const float* __restrict__ ws, int G, int C, int cw,
 
 // backward reduction: dbeta = sum g', dgamma = sum g' * xhat
 //   where g' = gy * act'(z), z recomputed from x
-template <typename T, int V, int ACT, bool DET>
+//   U > 1 as in bn_stats_vec_kernel
+template <typename T, int V, int ACT, bool DET, int U = 1>
 __global__ void __launch_bounds__(kBlock)
 bn_act_bwd_reduce_vec_kernel(const void* __restrict__ x,
                              const void* __restrict__ res,
@@ -351,12 +409,7 @@ bn_act_bwd_reduce_vec_kernel(const void* __restrict__ x,
         const Vec* gv = static_cast<const Vec*>(gy);
         const Vec* rv = static_cast<const Vec*>(res);
         const int rstride = lm.rstride();
-        for (int64_t m = lm.row0(); m < M; m += rstride) {
-          const int64_t off = m * Cv + lm.col();
-          const Vec xval = xv[off];
-          const Vec gval = gv[off];
-          Vec rval;
-          if constexpr (ACT == ACT_ADD_RELU) rval = rv[off];
+        auto add_row = [&](const Vec& xval, const Vec& rval, const Vec& gval) {
 #pragma unroll
           for (int j = 0; j < V; ++j) {
             const float xh = ((float)xval.v[j] - mu[j]) * is[j];
@@ -366,6 +419,29 @@ bn_act_bwd_reduce_vec_kernel(const void* __restrict__ x,
             db[j] += g;
             dg[j] += g * xh;
           }
+        };
+        int64_t m = lm.row0();
+        if constexpr (U > 1) {
+          for (; m + (int64_t)(U - 1) * rstride < M; m += (int64_t)U * rstride) {
+            Vec xval[U], gval[U], rval[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+              const int64_t off = (m + (int64_t)u * rstride) * Cv + lm.col();
+              xval[u] = xv[off];
+              gval[u] = gv[off];
+              if constexpr (ACT == ACT_ADD_RELU) rval[u] = rv[off];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) add_row(xval[u], rval[u], gval[u]);
+          }
+        }
+        for (; m < M; m += rstride) {
+          const int64_t off = m * Cv + lm.col();
+          const Vec xval = xv[off];
+          const Vec gval = gv[off];
+          Vec rval;
+          if constexpr (ACT == ACT_ADD_RELU) rval = rv[off];
+          add_row(xval, rval, gval);
         }
       });
 }
@@ -444,6 +520,78 @@ bn_join_stats_vec_kernel(const void* __restrict__ y_dec,
 // 8 more live registers per row, so it does not unroll.
 constexpr int fwd_unroll(int act) { return act == ACT_ADD_RELU ? 1 : 3; }
 constexpr int dx_unroll(int act) { return act == ACT_ADD_RELU ? 1 : 2; }
+// Rows in flight in the small-layer reductions: their few hundred
+// workgroups leave the memory parallelism to the thread.
+constexpr int red_unroll(int act) { return act == ACT_ADD_RELU ? 2 : 4; }
+
+// Where the normalize / dx kernels get their per-channel sums. WS = false:
+// finished values from an earlier launch. WS = true (small-layer path):
+// the G partials ws[G][2][C] of a DET reduction, which the workgroup adds
+// itself (ws_prologue); the workgroups with blockIdx.x == 0 store the
+// finished values, and with them the running statistics and the counter.
+template <bool WS>
+struct BnFwdStats {
+  const float* __restrict__ mean;
+  const float* __restrict__ invstd;
+};
+template <>
+struct BnFwdStats<true> {
+  const float* __restrict__ ws;
+  int G;
+  float* __restrict__ mean;          // out, saved for backward
+  float* __restrict__ invstd;        // out
+  float* __restrict__ running_mean;  // may be null, with running_var
+  float* __restrict__ running_var;
+  int64_t* __restrict__ num_batches_tracked;  // may be null
+  float eps, momentum;
+};
+template <bool WS>
+struct BnBwdSums {
+  const float* __restrict__ red;  // (2,C)
+};
+template <>
+struct BnBwdSums<true> {
+  const float* __restrict__ ws;
+  int G;
+  float* __restrict__ red;  // out (2,C)
+};
+
+// One entry of the (2, C) sums from its G partials, ascending g: eight
+// loads are issued ahead of their adds, the adds stay in order.
+__device__ __forceinline__ float ws_sum(const float* __restrict__ p, int G,
+                                        int64_t step) {
+  float t = 0.0f;
+  int g = 0;
+  for (; g + 7 < G; g += 8, p += 8 * step) {
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = p[u * step];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) t += v[u];
+  }
+  for (; g < G; ++g, p += step) t += *p;
+  return t;
+}
+
+// Prologue of the WS instantiations: the workgroup's nch = ncv*V channels
+// of both sums go to s[0..nch) and s[64V..64V+nch), one entry per thread
+// and pass, each by ws_sum — an order that depends on G alone. Every
+// thread of the block arrives here, idle lanes included; they retire
+// after the barrier.
+template <int V, typename LM>
+__device__ __forceinline__ void ws_prologue(const LM& lm,
+                                            const float* __restrict__ ws,
+                                            int G, int C,
+                                            float (&s)[2 * 64 * V]) {
+  const int nch = lm.ncv * V;
+  const float* base = ws + lm.c0v * V;
+  for (int i = threadIdx.x; i < 2 * nch; i += kBlock) {
+    const int which = i >= nch ? 1 : 0;
+    const int ci = i - which * nch;
+    s[which * 64 * V + ci] = ws_sum(base + which * C + ci, G, 2 * (int64_t)C);
+  }
+  __syncthreads();
+}
 
 template <typename T, int V, int ACT>
 __device__ __forceinline__ BnVec<T, V> bn_fwd_vec(
@@ -460,24 +608,48 @@ __device__ __forceinline__ BnVec<T, V> bn_fwd_vec(
 }
 
 // also the eval-mode kernel: mean/invstd are then the running statistics
-template <typename T, int V, int ACT, int U>
+template <typename T, int V, int ACT, int U, bool WS = false>
 __global__ void __launch_bounds__(kBlock)
 bn_act_fwd_vec_kernel(const void* __restrict__ x, const void* __restrict__ res,
-                      const float* __restrict__ mean,
-                      const float* __restrict__ invstd,
+                      const BnFwdStats<WS> st,
                       const float* __restrict__ gamma,
                       const float* __restrict__ beta, void* __restrict__ y,
                       int64_t M, int C, int cgv) {
   using Vec = BnVec<T, V>;
   const int Cv = C / V;
   const LaneMap<int64_t, int64_t> lm(Cv, cgv);
-  if (!lm.active()) return;
-  const int cb = lm.col() * V;
   float mu[V], is[V], ga[V], be[V];
+  if constexpr (WS) {
+    __shared__ float s_sum[2 * 64 * V];
+    ws_prologue<V>(lm, st.ws, st.G, C, s_sum);
+    if (!lm.active()) return;
+    // the first row of threads of the blockIdx.x == 0 workgroups owns the
+    // per-channel outputs
+    const bool owner = blockIdx.x == 0 && threadIdx.x < cgv;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const int cl = lm.lane_cv * V + j;
+      const BnMoments mo =
+          bn_moments(s_sum[cl], s_sum[64 * V + cl], M, st.eps);
+      mu[j] = mo.mu;
+      is[j] = mo.invstd;
+      if (owner)
+        bn_store_channel(mo, lm.col() * V + j, st.mean, st.invstd,
+                         st.running_mean, st.running_var, M, st.momentum);
+    }
+    if (owner && blockIdx.y == 0 && threadIdx.x == 0 &&
+        st.num_batches_tracked)
+      *st.num_batches_tracked += 1;
+  } else {
+    if (!lm.active()) return;
+  }
+  const int cb = lm.col() * V;
 #pragma unroll
   for (int j = 0; j < V; ++j) {
-    mu[j] = mean[cb + j];
-    is[j] = invstd[cb + j];
+    if constexpr (!WS) {
+      mu[j] = st.mean[cb + j];
+      is[j] = st.invstd[cb + j];
+    }
     ga[j] = gamma[cb + j];
     be[j] = beta[cb + j];
   }
@@ -527,7 +699,7 @@ __device__ __forceinline__ void bn_dx_vec(
   }
 }
 
-template <typename T, int V, int ACT, int U>
+template <typename T, int V, int ACT, int U, bool WS = false>
 __global__ void __launch_bounds__(kBlock)
 bn_act_bwd_dx_vec_kernel(const void* __restrict__ x,
                          const void* __restrict__ res,
@@ -536,24 +708,43 @@ bn_act_bwd_dx_vec_kernel(const void* __restrict__ x,
                          const float* __restrict__ invstd,
                          const float* __restrict__ gamma,
                          const float* __restrict__ beta,
-                         const float* __restrict__ red,  // (2,C)
+                         const BnBwdSums<WS> sums,
                          void* __restrict__ dx, void* __restrict__ dres,
                          int64_t M, int C, int cgv) {
   using Vec = BnVec<T, V>;
   const int Cv = C / V;
   const float invM = 1.0f / (float)M;
   const LaneMap<int64_t, int64_t> lm(Cv, cgv);
-  if (!lm.active()) return;
-  const int cb = lm.col() * V;
   float mu[V], is[V], ga[V], be[V], r0[V], r1[V];
+  if constexpr (WS) {
+    __shared__ float s_sum[2 * 64 * V];
+    ws_prologue<V>(lm, sums.ws, sums.G, C, s_sum);
+    if (!lm.active()) return;
+    const bool owner = blockIdx.x == 0 && threadIdx.x < cgv;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const int cl = lm.lane_cv * V + j;
+      r0[j] = s_sum[cl];
+      r1[j] = s_sum[64 * V + cl];
+      if (owner) {
+        sums.red[lm.col() * V + j] = r0[j];
+        sums.red[C + lm.col() * V + j] = r1[j];
+      }
+    }
+  } else {
+    if (!lm.active()) return;
+  }
+  const int cb = lm.col() * V;
 #pragma unroll
   for (int j = 0; j < V; ++j) {
     mu[j] = mean[cb + j];
     is[j] = invstd[cb + j];
     ga[j] = gamma[cb + j];
     be[j] = beta[cb + j];
-    r0[j] = red[cb + j];
-    r1[j] = red[C + cb + j];
+    if constexpr (!WS) {
+      r0[j] = sums.red[cb + j];
+      r1[j] = sums.red[C + cb + j];
+    }
   }
   const Vec* xv = static_cast<const Vec*>(x) + lm.col();
   const Vec* rv = static_cast<const Vec*>(res) + lm.col();
@@ -678,8 +869,9 @@ void launch_bn_act_fwd(const void* x, const void* res, const float* mean,
 #define BN_LAUNCH(A)                                                          \
   hipLaunchKernelGGL((bn_act_fwd_vec_kernel<T, V, A, fwd_unroll(A)>),         \
                      grid_rows_v(M, Cv, cgv, kMaxGridStream, max_blocks),     \
-                     dim3(kBlock), 0, s, x, res, mean, invstd, gamma, beta, y, \
-                     M, C, cgv)
+                     dim3(kBlock), 0, s, x, res,                              \
+                     BnFwdStats<false>{mean, invstd}, gamma, beta, y, M, C,   \
+                     cgv)
   BN_VEC_SWITCH(T, C, BN_ACT_SWITCH(act, BN_LAUNCH))
 #undef BN_LAUNCH
 }
@@ -710,7 +902,7 @@ void launch_bn_act_bwd_dx(const void* x, const void* res, const void* gy,
   hipLaunchKernelGGL((bn_act_bwd_dx_vec_kernel<T, V, A, dx_unroll(A)>),     \
                      grid_rows_v(M, Cv, cgv, kMaxGridStream, max_blocks),   \
                      dim3(kBlock), 0, s, x, res, gy, mean, invstd, gamma,   \
-                     beta, red, dx, dres, M, C, cgv)
+                     beta, BnBwdSums<false>{red}, dx, dres, M, C, cgv)
   BN_VEC_SWITCH(T, C, BN_ACT_SWITCH(act, BN_LAUNCH))
 #undef BN_LAUNCH
 }
@@ -729,7 +921,190 @@ void launch_bn_join_stats(const void* y_dec, const void* y_base,
           s, y_dec, y_base, bias, x, sums, M, HW, S, C, cgv))
 }
 
+// ---------------------------------------------------------------------------
+// small-layer path: the plan and its four launchers
+// ---------------------------------------------------------------------------
+
+// The plan for (M, C) of T, from the sweep in profiles/r14_bn_small.md.
+//   G:         a consumer workgroup reads G * 2 * nch * 4 bytes of partials
+//              (nch = its channels), so G = budget / (8 * nch): 32 KiB, or
+//              64 KiB for tensors of 8 MiB and more, where the reduction
+//              needs the workgroups more than the consumer minds the
+//              reads. That is 8..128, a multiple of the 8 loads ws_sum
+//              keeps in flight.
+//   reduction: channel chunks of 4 vectors (64 bytes of a row) on
+//              blockIdx.y, which gives the few partial rows the most
+//              workgroups; wider where a thread would be left without a
+//              row, and G halved where even that leaves it none.
+//   consumer:  today's lane map, kSmallRows rows per thread, at most
+//              kSmallMaxConsumers workgroups in all.
+// "small" is the size rule alone: every encoder, neck and first-decoder
+// shape up to 12.6 MB beats today's path by 1.5-4x in device time; beyond
+// kSmallMaxBytes the plan is unmeasured and today's path stays.
+constexpr int kSmallRows = 4;
+constexpr int kSmallMaxConsumers = 1024;
+constexpr int kSmallPrologueBytes = 32 << 10;
+constexpr int64_t kSmallWideBytes = (int64_t)8 << 20;  // budget doubles
+constexpr int kSmallMinCgv = 4;
+constexpr int64_t kSmallMaxBytes = (int64_t)16 << 20;
+constexpr int kSmallMaxG = 4096;  // what a forced G may ask for
+
+struct BnSmallPlan {
+  bool small;
+  int G, cgv, grid_x;
+};
+
+inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+template <typename T>
+BnSmallPlan small_plan(int64_t M, int C) {
+  BN_VEC_SWITCH(T, C, {
+    const int64_t bytes = M * C * (int64_t)sizeof(T);
+    const int nch = (Cv < cgv ? Cv : cgv) * V;
+    const int budget =
+        kSmallPrologueBytes * (bytes >= kSmallWideBytes ? 2 : 1);
+    int G = budget / (8 * nch);
+    G = G < 1 ? 1 : G;
+    int rc = cgv < kSmallMinCgv ? cgv : kSmallMinCgv;
+    while (rc < cgv && M < (int64_t)G * (kBlock / rc)) rc <<= 1;
+    while (G > 1 && M < (int64_t)G * (kBlock / rc)) G >>= 1;
+    int64_t consumers = ceil_div(M * Cv, (int64_t)kBlock * kSmallRows);
+    consumers = consumers < kSmallMaxConsumers ? consumers : kSmallMaxConsumers;
+    const int64_t gx = consumers / ceil_div(Cv, cgv);
+    return BnSmallPlan{bytes <= kSmallMaxBytes, G, rc,
+                       (int)(gx < 1 ? 1 : gx)};
+  })
+}
+
+// grid (G, channel chunks of cgv_r vectors): ws[G][2][C], unfilled
+template <typename T>
+void launch_bn_stats_partials(const void* x, float* ws, int64_t M, int C,
+                              int G, int cgv_r, hipStream_t s) {
+  BN_VEC_SWITCH(
+      T, C,
+      hipLaunchKernelGGL((bn_stats_vec_kernel<T, V, true, 4>),
+                         dim3(G, (Cv + cgv_r - 1) / cgv_r), dim3(kBlock), 0, s,
+                         x, ws, M, C, cgv_r))
+}
+
+template <typename T>
+void launch_bn_act_fwd_ws(const void* x, const void* res,
+                          const BnFwdStats<true>& st, const float* gamma,
+                          const float* beta, void* y, int64_t M, int C,
+                          int act, int grid_x, hipStream_t s) {
+#define BN_LAUNCH(A)                                                       \
+  hipLaunchKernelGGL((bn_act_fwd_vec_kernel<T, V, A, fwd_unroll(A), true>), \
+                     dim3(grid_x, (Cv + cgv - 1) / cgv), dim3(kBlock), 0, s, \
+                     x, res, st, gamma, beta, y, M, C, cgv)
+  BN_VEC_SWITCH(T, C, BN_ACT_SWITCH(act, BN_LAUNCH))
+#undef BN_LAUNCH
+}
+
+template <typename T>
+void launch_bn_act_bwd_reduce_partials(const void* x, const void* res,
+                                       const void* gy, const float* mean,
+                                       const float* invstd,
+                                       const float* gamma, const float* beta,
+                                       float* ws, int64_t M, int C, int act,
+                                       int G, int cgv_r, hipStream_t s) {
+#define BN_LAUNCH(A)                                                         \
+  hipLaunchKernelGGL(                                                        \
+      (bn_act_bwd_reduce_vec_kernel<T, V, A, true, red_unroll(A)>),          \
+      dim3(G, (Cv + cgv_r - 1) / cgv_r), dim3(kBlock), 0, s, x, res, gy,     \
+      mean, invstd, gamma, beta, ws, M, C, cgv_r)
+  BN_VEC_SWITCH(T, C, BN_ACT_SWITCH(act, BN_LAUNCH))
+#undef BN_LAUNCH
+}
+
+template <typename T>
+void launch_bn_act_bwd_dx_ws(const void* x, const void* res, const void* gy,
+                             const float* mean, const float* invstd,
+                             const float* gamma, const float* beta,
+                             const BnBwdSums<true>& sums, void* dx, void* dres,
+                             int64_t M, int C, int act, int grid_x,
+                             hipStream_t s) {
+#define BN_LAUNCH(A)                                                          \
+  hipLaunchKernelGGL(                                                         \
+      (bn_act_bwd_dx_vec_kernel<T, V, A, dx_unroll(A), true>),                \
+      dim3(grid_x, (Cv + cgv - 1) / cgv), dim3(kBlock), 0, s, x, res, gy,     \
+      mean, invstd, gamma, beta, sums, dx, dres, M, C, cgv)
+  BN_VEC_SWITCH(T, C, BN_ACT_SWITCH(act, BN_LAUNCH))
+#undef BN_LAUNCH
+}
+
+// a power of two in [1, 64]
+inline bool valid_cgv(int cgv) {
+  return cgv >= 1 && cgv <= 64 && (cgv & (cgv - 1)) == 0;
+}
+inline bool valid_grid(int g) { return g >= 1 && g <= kSmallMaxG; }
+// the channel chunks of a reduction fit grid.y (Cv <= C)
+inline bool valid_chunks(int C, int cgv) { return C / cgv < 65535; }
+
 }  // namespace
+
+extern "C" int mine_bn_small_plan(int64_t M, int C, int elem, int* G, int* cgv,
+                                  int* grid_x) {
+  BnSmallPlan p{};
+  MINE_ELEM_SWITCH(elem, p = small_plan<T>(M, C))
+  *G = p.G;
+  *cgv = p.cgv;
+  *grid_x = p.grid_x;
+  return p.small ? 1 : 0;
+}
+
+extern "C" int mine_bn_stats_partials(const void* x, float* ws, int64_t M,
+                                      int C, int G, int cgv, int elem,
+                                      hipStream_t s) {
+  if (!valid_grid(G) || !valid_cgv(cgv) || !valid_chunks(C, cgv))
+    return kNoKernel;
+  MINE_ELEM_SWITCH(elem, launch_bn_stats_partials<T>(x, ws, M, C, G, cgv, s))
+  return kLaunched;
+}
+
+extern "C" int mine_bn_act_fwd_ws(const void* x, const void* res,
+                                  const float* ws, int G, const float* gamma,
+                                  const float* beta, void* y, float* mean,
+                                  float* invstd, float* running_mean,
+                                  float* running_var,
+                                  int64_t* num_batches_tracked, int64_t M,
+                                  int C, int act, int grid_x, float eps,
+                                  float momentum, int elem, hipStream_t s) {
+  if (!valid_grid(G) || !valid_grid(grid_x)) return kNoKernel;
+  const BnFwdStats<true> st{ws,           G,           mean,
+                            invstd,       running_mean, running_var,
+                            num_batches_tracked, eps,  momentum};
+  MINE_ELEM_SWITCH(elem, launch_bn_act_fwd_ws<T>(x, res, st, gamma, beta, y, M,
+                                                 C, act, grid_x, s))
+  return kLaunched;
+}
+
+extern "C" int mine_bn_act_bwd_reduce_partials(
+    const void* x, const void* res, const void* gy, const float* mean,
+    const float* invstd, const float* gamma, const float* beta, float* ws,
+    int64_t M, int C, int act, int G, int cgv, int elem, hipStream_t s) {
+  if (!valid_grid(G) || !valid_cgv(cgv) || !valid_chunks(C, cgv))
+    return kNoKernel;
+  MINE_ELEM_SWITCH(elem, launch_bn_act_bwd_reduce_partials<T>(
+                             x, res, gy, mean, invstd, gamma, beta, ws, M, C,
+                             act, G, cgv, s))
+  return kLaunched;
+}
+
+extern "C" int mine_bn_act_bwd_dx_ws(const void* x, const void* res,
+                                     const void* gy, const float* mean,
+                                     const float* invstd, const float* gamma,
+                                     const float* beta, const float* ws, int G,
+                                     float* red, void* dx, void* dres,
+                                     int64_t M, int C, int act, int grid_x,
+                                     int elem, hipStream_t s) {
+  if (!valid_grid(G) || !valid_grid(grid_x)) return kNoKernel;
+  const BnBwdSums<true> sums{ws, G, red};
+  MINE_ELEM_SWITCH(elem, launch_bn_act_bwd_dx_ws<T>(x, res, gy, mean, invstd,
+                                                    gamma, beta, sums, dx,
+                                                    dres, M, C, act, grid_x,
+                                                    s))
+  return kLaunched;
+}
 
 extern "C" int mine_bn_reduce_grid(int64_t M, int C, int max_blocks,
                                    int elem) {

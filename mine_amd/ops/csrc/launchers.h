@@ -200,6 +200,45 @@ int mine_bn_act_bwd_dx(const void* x, const void* res, const void* gy,
                        void* dx, void* dres, int64_t M, int C, int act,
                        int max_blocks, int elem, hipStream_t s);
 
+// Small-layer path: two launches per direction, order-fixed, no fill. The
+// reductions store G partials into ws (G,2,C), unfilled; the consumers add
+// them in ascending g. G and grid_x in [1, 4096], cgv a power of two in
+// [1, 64]; otherwise kNoKernel.
+//
+// The plan for (M, C) of `elem`: *G partial rows, the reduction's channel
+// chunk *cgv (vectors), the consumer's *grid_x. Returns 1 where the layer
+// should take the path, 0 where today's kernels win (the plan is valid
+// either way), kNoKernel for an unknown elem.
+int mine_bn_small_plan(int64_t M, int C, int elem, int* G, int* cgv,
+                       int* grid_x);
+// x (M,C) -> ws (G,2,C) partial (sum, sumsq)
+int mine_bn_stats_partials(const void* x, float* ws, int64_t M, int C, int G,
+                           int cgv, int elem, hipStream_t s);
+// ws (G,2,C) partial (sum, sumsq) -> y (M,C), mean, invstd (C); updates
+// running_mean/running_var (C) once and adds 1 to num_batches_tracked (1),
+// each where not null. res as in mine_bn_act_fwd.
+int mine_bn_act_fwd_ws(const void* x, const void* res, const float* ws, int G,
+                       const float* gamma, const float* beta, void* y,
+                       float* mean, float* invstd, float* running_mean,
+                       float* running_var, int64_t* num_batches_tracked,
+                       int64_t M, int C, int act, int grid_x, float eps,
+                       float momentum, int elem, hipStream_t s);
+// as mine_bn_act_bwd_reduce with det: ws (G,2,C) partial (dbeta, dgamma)
+int mine_bn_act_bwd_reduce_partials(const void* x, const void* res,
+                                    const void* gy, const float* mean,
+                                    const float* invstd, const float* gamma,
+                                    const float* beta, float* ws, int64_t M,
+                                    int C, int act, int G, int cgv, int elem,
+                                    hipStream_t s);
+// ws (G,2,C) partial (dbeta, dgamma) -> dx, dres as mine_bn_act_bwd_dx, and
+// red (2,C), the finished sums
+int mine_bn_act_bwd_dx_ws(const void* x, const void* res, const void* gy,
+                          const float* mean, const float* invstd,
+                          const float* gamma, const float* beta,
+                          const float* ws, int G, float* red, void* dx,
+                          void* dres, int64_t M, int C, int act, int grid_x,
+                          int elem, hipStream_t s);
+
 // ---------------------------------------------------------------------------
 // head_kernels.hip — z f32, bf16 or fp16; the packed MPI is f32
 // ---------------------------------------------------------------------------
